@@ -2,7 +2,15 @@
 plus the sqrt-PST commit+open seconds at 2^20 (configs[2]) and 2^24
 (configs[3]) variables, with the C++ CPU restatement timed beside them.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline JSON
+line (metric / value / unit / ms_per_step / the per-stage device spans of the
+timed steps).  --dump-outputs DIR also writes what the last timed step computed
+(DIR/msm_out.npy, see dump_outputs).  Everything else described below -- the
+single-call latency, the parity spot check, the roofline and compute columns,
+the sqrt-PST / R1CS / Groth16 legs, the multi-rank legs and the CPU baseline --
+runs only with --full (each leg still has its --no-* switch there).
 
 A step = one variable-base G1 MSM over 2^20 points (canonical Fr scalars,
 Montgomery affine bases, both resident in HBM before the timed region) -- the
@@ -78,6 +86,11 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--log-n", type=int, default=LOG_N)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result as DIR/<name>.npy (float64, exact)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs: latency, parity check, roofline, sqrt-PST, R1CS, Groth16, "
+                         "multi-rank legs, CPU baseline (the --no-* switches apply to these)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--no-pst", action="store_true", help="skip the sqrt-PST commit+open leg")
     ap.add_argument("--pst-log-n", type=int, default=20)
@@ -88,7 +101,10 @@ def parse():
     ap.add_argument("--no-groth16", action="store_true", help="skip the Groth16 prove leg")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: exercise the launcher / rendezvous / timing plumbing only (gloo)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _free_port():
@@ -191,6 +207,17 @@ def _max_over_ranks(dist, dev, x):
     return float(t.item())
 
 
+def dump_outputs(path, rank, out):
+    """--dump-outputs: what a caller of the timed path receives from its last
+    step -- the MSM result, one affine G1 point as 12 uint64 Montgomery limbs
+    (x | y, tpst_g1_msm_dev_async's 96-B output) -- written as msm_out.npy
+    (rank 0; msm_out_rank<r>.npy for the other ranks): float64[24], the 32-bit
+    halves of the limbs, low half first, so every value is exact."""
+    os.makedirs(path, exist_ok=True)
+    words = np.ascontiguousarray(out, dtype="<u8").view("<u4").astype(np.float64)
+    np.save(os.path.join(path, "msm_out.npy" if rank == 0 else "msm_out_rank%d.npy" % rank), words)
+
+
 def dry_run(args):
     """CPU rehearsal of the multi-rank plumbing (tests/test_distributed.py):
     gloo rendezvous, barrier-bracketed timing, max over ranks, one JSON line."""
@@ -285,6 +312,37 @@ def main():
     ctx.profile(False)
     stages = ctx.profile_read()
     elapsed = _max_over_ranks(dist, dev, t1 - t0)
+    out = d_out.cpu().numpy().view(np.uint64)  # the last timed step's result
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, out)
+    ms_step = elapsed / args.steps * 1e3
+    value = world * n * args.steps / elapsed / 1e6  # Mscalar/s, whole job
+    result = {
+        "metric": METRIC,
+        "value": round(value, 3),
+        "unit": "Mscalar/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u32",
+        "data": "synthetic (SplitMix64 uniform Fr scalars, bases b_i*G1 generated on device)",
+        "config": {"workload": "single BLS12-377 G1 Pippenger MSM, 2^%d points per GPU (BASELINE configs[1])"
+                               % args.log_n,
+                   "n_points": n, "curve": "BLS12-377 G1", "window_bits": 16,
+                   "parallelism": "independent MSM per rank" if world > 1 else "1 GPU"},
+        "stages_ms_per_step": {k: round(v[0] / max(v[1], 1), 4) for k, v in stages.items() if v[1]},
+    }
+    if not args.full:  # the plain run ends here
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return 0
     # one MSM alone (synchronised after each call): the latency; the timed
     # loop above overlaps call i's latency-bound tail with call i+1
     # (tpst_g1_msm_dev pipelining)
@@ -300,7 +358,6 @@ def main():
     # correctness spot check of this rank's result against the size-independent
     # property MSM(b_i G) = (sum s_i b_i) G, verified with the library's
     # generator multiplication (a different code path from the MSM)
-    out = d_out.cpu().numpy().view(np.uint64)
     from testudo_amd.encoding import fr_array
     R = 0x12AB655E9A2CA55660B44D1E5C37B00159AA76FED00000010A11800000000001
     s_int = sc.astype(object)
@@ -332,8 +389,6 @@ def main():
             dist.destroy_process_group()
         return 0
 
-    ms_step = elapsed / args.steps * 1e3
-    value = world * n * args.steps / elapsed / 1e6  # Mscalar/s, whole job
     acc_ms, acc_cnt = stages["bucket_acc"]
     acc_avg_ms = acc_ms / max(acc_cnt, 1)
     alg_bytes = n * BYTES_PER_PAIR + 96
@@ -380,23 +435,7 @@ def main():
                         "valu_issue_frac_note": "instructions, not issue slots (v_mad_u64_u32 = 2 slots)"})
     compute.update(valu_slots(PMC_VALU_K2, acc_avg_ms, rates))
 
-    result = {
-        "metric": METRIC,
-        "value": round(value, 3),
-        "unit": "Mscalar/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_step, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u32",
-        "data": "synthetic (SplitMix64 uniform Fr scalars, bases b_i*G1 generated on device)",
-        "config": {"workload": "single BLS12-377 G1 Pippenger MSM, 2^%d points per GPU (BASELINE configs[1])"
-                               % args.log_n,
-                   "n_points": n, "curve": "BLS12-377 G1", "window_bits": c_bits,
-                   "parallelism": "independent MSM per rank" if world > 1 else "1 GPU"},
+    result.update({
         "parity_ok": parity_ok,
         "latency_ms_single_call": round(latency_ms, 4),
         "pipelining": ("consecutive tpst_g1_msm_dev_async calls (the pipelined entry point; tpst_g1_msm_dev is "
@@ -405,7 +444,6 @@ def main():
                        "accumulation under call i's last-window-group tail (fixup, bucket reduction, window chain, "
                        "affine output); ms_per_step is the steady state, latency_ms_single_call one call "
                        "synchronised alone"),
-        "stages_ms_per_step": {k: round(v[0] / max(v[1], 1), 4) for k, v in stages.items() if v[1]},
         "roofline": {"bound": "valu-int32", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic,
                      "traffic_source": (os.path.relpath(PMC_FILE, ROOT) if pmc else None),
@@ -415,7 +453,7 @@ def main():
                               "is the per-launch ratio); HBM column secondary: the kernel is bound by 32-bit integer "
                               "VALU issue (compute.valu_slot_frac)")},
         "compute": compute,
-    }
+    })
     if world > 1 and os.environ.get("TPST_BENCH_SHARED_GPU") == "1":
         result["rehearsal"] = ("%d ranks sharing %d GPU(s) over gloo (TPST_BENCH_SHARED_GPU=1): a correctness "
                                "rehearsal of the multi-rank legs; the timings are NOT scaling numbers"

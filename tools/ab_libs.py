@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def run(label, path):
     env = dict(os.environ, TPST_LIB_PATH=os.path.join(ROOT, path))
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu", "--no-pst", "--no-sharded",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu", "--no-pst", "--no-sharded",
                         "--no-r1cs", "--no-groth16", "--steps", "20", "--warmup", "3"], capture_output=True, text=True,
                        env=env, timeout=300)
     line = [x for x in r.stdout.splitlines() if x.startswith("{")]

@@ -9,4 +9,4 @@ for i in 1 2; do
 timeout -k 10 400 python -u tools/commit_sweep.py 24 TPST_COMMIT_BLOCKS=1 >> $OUT/ab_blocks24.txt 2>&1 || exit 1
 timeout -k 10 400 python -u tools/commit_sweep.py 20 TPST_COMMIT_BLOCKS=1 >> $OUT/ab_blocks20.txt 2>&1 || exit 1
 done
-timeout -k 10 600 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err || exit 1
+timeout -k 10 600 python -u bench.py --full >$OUT/bench.json 2> $OUT/bench.err || exit 1

@@ -3,7 +3,7 @@
 # steps:
 #   tests   pytest -m gpu + smoke
 #   msmtests  only the MSM tests of tests/test_gpu.py
-#   bench   default bench.py (JSON line -> bench.json)
+#   bench   bench.py --full, every leg (JSON line -> bench.json)
 #   prof    rocprofv3 kernel traces + stats: MSM bench, 2^20 and 2^24 commit+open
 #   pmc     PMC passes (FETCH_SIZE, WRITE_SIZE, VALU, stall counters) on the MSM bench
 #   k1pmc   PMC passes (FETCH_SIZE, WRITE_SIZE, VALU) on the 2^24 commit (K1)
@@ -18,7 +18,7 @@ shift
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 R=$GRAFT_REPO_ROOT
-SHORT="$R/bench.py --no-cpu --no-pst --no-sharded --no-r1cs --no-groth16 --steps 5 --warmup 2"
+SHORT="$R/bench.py --full --no-cpu --no-pst --no-sharded --no-r1cs --no-groth16 --steps 5 --warmup 2"
 K1="$R/tools/prof_open.py 24 1"
 export TMPDIR=/tmp
 for step in "$@"; do
@@ -30,7 +30,7 @@ for step in "$@"; do
     msmtests)
       cd $R && timeout -k 10 600 python -u -m pytest tests/test_gpu.py -x -v --timeout 300 --timeout-method thread -k "msm" > $OUT/msm_tests.log 2>&1 || exit 1 ;;
     bench)
-      cd $R && timeout -k 10 600 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err || exit 1 ;;
+      cd $R && timeout -k 10 600 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err || exit 1 ;;
     prof)
       cd /tmp
       timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_msm -o run -- python3 $SHORT > $OUT/prof_msm.log 2>&1 || exit 1
