@@ -478,6 +478,14 @@ int tpst_microbench_wave_phases(tpst_ctx* ctx, int op, int iters, uint64_t* cycl
 /* Self-test of the two device Fq inverses: n Montgomery-form values (6 words
  * each) -> their inverses by the lone-lane routine and by the wave routine. */
 int tpst_selftest_inv(tpst_ctx* ctx, size_t n, const uint64_t* in, uint64_t* out_lane, uint64_t* out_wave);
+/* Self-tests of the device arithmetic below the kernels: one field operation
+ * (op = family * 32 + index) or one curve operation (op = form * 16 + index)
+ * per element on n caller-chosen operands, words exactly as the kernels hold
+ * them.  The op numbers and the words per operand and result are those of
+ * csrc/selftest_ops.h (field_in_words / field_out_words / curve_words).  A bad
+ * op, a null pointer or n == 0 is TPST_E_ARG (q may be null for glv_split). */
+int tpst_selftest_field(tpst_ctx* ctx, int op, size_t n, const uint64_t* a, const uint64_t* b, uint64_t* out);
+int tpst_selftest_curve(tpst_ctx* ctx, int op, size_t n, const uint64_t* p, const uint64_t* q, uint64_t* out);
 
 /* Per-stage HIP-event timing of the MSM pipeline on the context's stream.
  * stage: 0 decompose, 1 sort, 2 bucket bounds, 3 bucket accumulation (the

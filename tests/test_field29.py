@@ -52,6 +52,45 @@ def test_field29_ops_and_inverse(exe):
         assert got == exp, (a, b)
 
 
+def test_field29_constructed_edge_operands(exe):
+    """Radix-2^29 operands X, Y chosen in the R = 2^377 domain itself
+    (arith_vectors.py asserts each class's property from integers): products,
+    squares and product sums whose reduction word m_k is zero for every
+    column k and for pairs of columns -- where the carry ceil(acc / 2^29)
+    differs from floor(acc / 2^29) + 1 --, the bound cases of mul_sum /
+    mul_sub, and values Y with 128 Y within 128 of a multiple of p, the
+    q - 1 arm of to_std's quotient estimate.  The exe applies from_std to
+    its input, so it is fed V = X 2^7 mod p."""
+    import arith_vectors as V
+    F = V.F29
+    rng = random.Random(31)
+    prs = [(P - 1, P - 1), (P - 1, 0), (0, P - 1), (F.R % P, F.R % P)]
+    for cols in V.mk0_columns(F):
+        prs += V.mul_mk0(F, rng, cols)
+        a = rng.randrange(1, P) | 1
+        prs += [(a, b) for b in V.solve_mk0(F, rng, cols, a * a, a, "mul_sum")]
+        b = rng.randrange(1, P) | 1
+        prs += [(a2, b) for a2 in V.solve_mk0(F, rng, cols, b * (P - b), b, "mul_sub")]
+    sq = V.sqr_m0(F, rng)
+    for k in range(1, F.n):
+        sq += V.sqr_mk0(F, rng, k)
+    prs += [(x, rng.randrange(P)) for x in sq]
+    for q in range(1, 128):
+        y = -(-q * P // 128)
+        assert min(128 * y % P, P - 128 * y % P) <= 128 and min(128 * (y - 1) % P, P - 128 * (y - 1) % P) <= 128
+        prs += [(y, y - 1), (y - 1, y)]
+    assert len(prs) > 13 * 6 + 12 + 254
+    out = _run(exe, [(0, x * 128 % P, y * 128 % P) for x, y in prs])
+    Ri = F.Ri
+    for k, (x, y) in enumerate(prs):
+        got = [_parse(out[12 * k + j]) for j in range(12)]
+        v = x * 128 % P
+        exp = [x * y * Ri * 128 % P, x * x * Ri * 128 % P, (x + y) * 128 % P, (x - y) * 128 % P, v,
+               (pow(v, -1, P) * R * R % P) if v else 0, (x * y + x * x) * Ri * 128 % P,
+               (x * y - y * y) * Ri * 128 % P, x, v, (-x) * 128 % P, v]
+        assert got == exp, (hex(x), hex(y), [i for i in range(12) if got[i] != exp[i]])
+
+
 def test_field29_wave_stage_products_on_wide_operands(exe):
     rng = random.Random(30)
     rows = []

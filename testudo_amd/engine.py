@@ -186,6 +186,79 @@ class Context:
         self.check(self.lib.tpst_selftest_inv(self.h, len(vals), ptr(vals), ptr(ol), ptr(ow)), "tpst_selftest_inv")
         return ol, ow
 
+    def selftest_field(self, op: int, a: np.ndarray, b: np.ndarray = None) -> np.ndarray:
+        """one device field operation per row of a (and b): `op` and the u32
+        words per operand / result are SELFTEST_FIELD's (csrc/selftest_ops.h);
+        rows are u32 words, the result is (n, out words) u32"""
+        wi, wo = selftest_field_words(op)
+        a = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1, wi)
+        b = a if b is None else np.ascontiguousarray(b, dtype=np.uint32).reshape(-1, wi)
+        assert a.shape == b.shape
+        out = np.zeros((len(a), wo), dtype=np.uint32)
+        self.check(self.lib.tpst_selftest_field(self.h, op, len(a), _u32ptr(a), _u32ptr(b), _u32ptr(out)),
+                   "tpst_selftest_field")
+        return out
+
+    def selftest_curve(self, op: int, p: np.ndarray, q: np.ndarray = None) -> np.ndarray:
+        """one device curve operation (or glv_split) per row of p (and q), XYZZ
+        words in and out: `op` = SELFTEST_CURVE_FORMS[form] * 16 +
+        SELFTEST_CURVE_OPS[name] (csrc/selftest_ops.h)"""
+        w = selftest_curve_words(op)
+        p = np.ascontiguousarray(p, dtype=np.uint32).reshape(-1, w)
+        if q is not None:
+            q = np.ascontiguousarray(q, dtype=np.uint32).reshape(-1, w)
+            assert p.shape == q.shape
+        out = np.zeros((len(p), w), dtype=np.uint32)
+        self.check(self.lib.tpst_selftest_curve(self.h, op, len(p), _u32ptr(p), None if q is None else _u32ptr(q),
+                                                _u32ptr(out)), "tpst_selftest_curve")
+        return out
+
+
+def _u32ptr(a: np.ndarray):
+    assert a.dtype == np.uint32 and a.flags["C_CONTIGUOUS"] and a.size % 2 == 0
+    return a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+
+# Op numbers and word counts of tpst_selftest_field / tpst_selftest_curve.  The
+# single source is csrc/selftest_ops.h (the enums, field_in_words /
+# field_out_words / curve_words, field_op_valid / curve_op_valid); these
+# tables restate it for Python, and tests/test_selftest_ops.py compares them
+# with the header's values, read through the compiled host dispatch.
+SELFTEST_FIELD_FAMILIES = {"fq": 0, "fr": 1, "fq29": 2, "fq2": 3, "fq2p": 4}
+SELFTEST_FIELD = {}
+for _i, _n in enumerate(("mul", "sqr", "add", "sub", "neg", "to_mont", "from_mont")):
+    SELFTEST_FIELD["fq." + _n] = _i
+    SELFTEST_FIELD["fr." + _n] = 32 + _i
+for _i, _n in enumerate(("mul", "sqr", "mul_sum", "mul_sub", "add", "sub", "cneg", "p_minus", "to_std", "to_std_mul",
+                         "from_std", "roundtrip", "mul_sum4", "mul_sub4")):
+    SELFTEST_FIELD["fq29." + _n] = 64 + _i
+for _i, _n in enumerate(("mul", "sqr")):
+    SELFTEST_FIELD["fq2." + _n] = 96 + _i
+for _i, _n in enumerate(("mul", "is_zero", "eq")):
+    SELFTEST_FIELD["fq2p." + _n] = 128 + _i
+SELFTEST_CURVE_FORMS = {"fq": 0, "fq29_acc": 1, "fq29_pk": 2, "fq2": 3, "coop_fq29_acc": 4, "coop_fq2_acc": 5,
+                        "pair": 6, "glv": 7, "coop_fq29_pk": 8, "fq2_acc": 9}
+SELFTEST_CURVE_OPS = {"add_affine": 0, "add": 1, "dbl": 2, "dbl_affine": 3, "sub_affine": 4, "to_affine": 5}
+SELFTEST_GLV_SPLIT = 7 * 16
+
+
+def selftest_field_words(op: int):
+    """(u32 words per operand, per result) of a tpst_selftest_field op"""
+    fam, idx = op >> 5, op & 31
+    if fam == 1:
+        return 8, 8
+    if fam == 3:
+        return 24, 24
+    if fam == 4:
+        return 24, (24 if idx == 0 else 2)
+    return (24 if fam == 2 and idx in (12, 13) else 12), 12
+
+
+def selftest_curve_words(op: int) -> int:
+    """u32 words per element of p, q and the result of a tpst_selftest_curve op"""
+    form = op >> 4
+    return 8 if form == 7 else 96 if form in (3, 5, 6, 9) else 48
+
 
 class Gens:
     """MultiCommitGens {n, G, h} (commitments.rs:9-15) resident on the device,
