@@ -399,6 +399,44 @@ typedef struct {
 int tpst_r1cs_prove(tpst_ctx* ctx, tpst_r1cs* r1cs, const uint64_t* vars, const uint64_t* inputs,
                     tpst_transcript* tr, tpst_r1cs_proof* out);
 
+/* R1CSInstance::evaluate (r1csinstance.rs:308-311, SparseMatPolynomial::
+ * multi_evaluate): evals = (A, B, C)(rx, ry), 3 x 4 u64 canonical.  rx has
+ * log2(num_cons) entries, ry log2(2 num_vars), both MSB-first as tpst_eq_evals
+ * takes them.  Both eq tables and the gather-multiply-reduce over the resident
+ * CSR run on the device (no atomics: the value does not depend on the launch).
+ * TPST_E_ARG: a coordinate >= r, or an instance of another context. */
+int tpst_r1cs_evaluate(tpst_ctx* ctx, tpst_r1cs* r1cs, const uint64_t* rx, const uint64_t* ry, uint64_t* evals);
+/* R1CSInstance::is_sat (r1csinstance.rs:244-274): TPST_OK if Az * Bz = Cz in
+ * every row for z = vars || 1 || inputs || 0, TPST_E_VERIFY if not;
+ * TPST_E_ARG for a value >= r. */
+int tpst_r1cs_is_sat(tpst_ctx* ctx, tpst_r1cs* r1cs, const uint64_t* vars, const uint64_t* inputs);
+/* R1CSVerifierProof::verify as intended (r1csproof.rs:443-486) with the checks
+ * of R1CSVerificationCircuit::generate_constraints (constraints.rs:263-397)
+ * run natively on the host -- the transcript replay of tpst_r1cs_prove, both
+ * SumcheckInstanceProof::verify (sumcheck.rs:29-66), the derived rx / ry
+ * against the proof's (:317-319, :362-364), the two final claims (:328-340,
+ * :376-388 with z(ry) from eval_vars_at_ry and the sparse (1, inputs)
+ * polynomial of r1csproof.rs:390-398), the transcript state after the
+ * sum-checks -- then Polynomial::verify of the witness opening at ry[1..]
+ * (r1csproof.rs:469-480, tpst_pst_verify).  evals = (A, B, C)(rx, ry) is the
+ * caller's (SNARK mode, tests); `tr` is updated in place.  The fields r_abc
+ * and claims_phase2_z_abc are not read (the reference's verifier never sees
+ * them).
+ * TPST_OK: the proof verifies.  TPST_E_VERIFY: any failed check, a
+ * non-canonical Fr in the proof, the inputs or evals, or rounds_x / rounds_y /
+ * num_vars_log / the opening's m_col, m_row not matching the dimensions.
+ * TPST_E_ARG: null arguments, dimensions that are not powers of two or beyond
+ * TPST_R1CS_MAX_ROUNDS.  TPST_E_STATE: the SRS is not loaded for
+ * ceil(log2(num_vars) / 2) variables (as for tpst_r1cs_prove). */
+int tpst_r1cs_verify_evals(tpst_ctx* ctx, size_t num_cons, size_t num_vars, const uint64_t* inputs,
+                           size_t num_inputs, const uint64_t* evals, tpst_transcript* tr,
+                           const tpst_r1cs_proof* proof);
+/* TestudoNizk::verify (testudo_nizk.rs:136-157) minus the digest append:
+ * tpst_r1cs_evaluate at the proof's (rx, ry), then tpst_r1cs_verify_evals.
+ * Also TPST_E_ARG for an instance of another context. */
+int tpst_r1cs_verify(tpst_ctx* ctx, tpst_r1cs* r1cs, const uint64_t* inputs, tpst_transcript* tr,
+                     const tpst_r1cs_proof* proof);
+
 /* ---- Groth16 over BLS12-377 (csrc/groth16.hip) ----
  * The prover behind R1CSProof::prove_verifier (r1csproof.rs:374-434,
  * Groth16::<E>::prove at :421): ark-groth16 create_proof with the
@@ -489,7 +527,8 @@ int tpst_selftest_curve(tpst_ctx* ctx, int op, size_t n, const uint64_t* p, cons
 
 /* Per-stage HIP-event timing of the MSM pipeline on the context's stream.
  * stage: 0 decompose, 1 sort, 2 bucket bounds, 3 bucket accumulation (the
- * dominant kernel), 4 bucket reduction, 5 window combine, 6 K1 row sort. */
+ * dominant kernel), 4 bucket reduction, 5 window combine, 6 K1 row sort;
+ * 15 / 16: tpst_r1cs_evaluate's eq tables / its reduction and partial sum. */
 int tpst_profile_enable(tpst_ctx* ctx, int on);
 int tpst_profile_reset(tpst_ctx* ctx);
 int tpst_profile_read(tpst_ctx* ctx, int stage, double* total_ms, uint64_t* launches);

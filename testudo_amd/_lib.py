@@ -103,6 +103,10 @@ PROTOTYPES = [
     ("tpst_r1cs_free", None, [_vp]),
     ("tpst_r1cs_commit", C.c_int, [_vp, _vp, C.c_char_p, _sz, _u64p, C.POINTER(_sz), _u64p, C.POINTER(_sz)]),
     ("tpst_r1cs_prove", C.c_int, [_vp, _vp, _u64p, _u64p, _vp, _vp]),
+    ("tpst_r1cs_evaluate", C.c_int, [_vp, _vp, _u64p, _u64p, _u64p]),
+    ("tpst_r1cs_is_sat", C.c_int, [_vp, _vp, _u64p, _u64p]),
+    ("tpst_r1cs_verify_evals", C.c_int, [_vp, _sz, _sz, _u64p, _sz, _u64p, _vp, _vp]),
+    ("tpst_r1cs_verify", C.c_int, [_vp, _vp, _u64p, _vp, _vp]),
     ("tpst_groth16_setup", C.c_int, [_vp, _vp, _u64p, C.POINTER(_vp)]),
     ("tpst_groth16_pk_free", None, [_vp]),
     ("tpst_groth16_domain", C.c_int, [_vp, C.POINTER(_sz)]),

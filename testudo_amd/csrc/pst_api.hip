@@ -287,6 +287,12 @@ static int srs_install(tpst_ctx* ctx, int nv, const uint64_t* flat) {
 
 static SrsState* srs_of(tpst_ctx* ctx) { return srs_slot(ctx).get(); }
 
+// internal (r1cs.hip): the number of variables of the loaded SRS, or -1
+int tpst_internal_srs_nv(tpst_ctx* ctx) {
+  SrsState* st = srs_of(ctx);
+  return st ? st->nv : -1;
+}
+
 // scratch of the RNS G2 preparation (g2_prepare_scratch(n) bytes: residue
 // lines, ~53 KB per point) sized for the largest batch prepared since the
 // SRS was installed -- the install's 2^nv batch is released right after it

@@ -12,6 +12,11 @@
 //                     the r_A / r_B / r_C combination (r1csproof.rs:326-338) fused
 //   phase one         prove_cubic_with_additive_term (sumcheck.rs:67-148), comb tau (A B - C)
 //   phase two         prove_quad (sumcheck.rs:387-444), comb A B
+//
+// and the proof's verifier: R1CSInstance::evaluate (r1csinstance.rs:308-311) on
+// the device (eq tables + one gather-multiply-reduce over the CSR), is_sat, and
+// the checks of R1CSVerificationCircuit (constraints.rs:263-397) replayed on
+// the host before Polynomial::verify of the witness opening.
 #include <cstring>
 #include <memory>
 #include <vector>
@@ -224,6 +229,113 @@ __global__ void __launch_bounds__(SC_BS) k_sc_reduce(const uint32_t* __restrict_
     __syncthreads();
   }
   if (threadIdx.x < 3) store_f<Fr>(out + 8 * threadIdx.x, from_mont(sh[threadIdx.x][0]));
+}
+
+// ------------------------------------------------ R1CSInstance::evaluate ----
+// (A, B, C)(rx, ry) = sum_e val_e eq(rx, row_e) eq(ry, col_e)
+// (SparseMatPolynomial::multi_evaluate, r1csinstance.rs:308-311) over the CSR:
+// nnz + rows products instead of 2 nnz, no atomics, exact field sums -- the
+// result does not depend on the grid.
+constexpr int EV_BS = 256;               // 4 waves of 64
+#ifndef TPST_EV_MAX_BLOCKS
+#define TPST_EV_MAX_BLOCKS 128  // A/B builds: TPST_EXTRA_FLAGS=-DTPST_EV_MAX_BLOCKS=n
+#endif
+constexpr unsigned EV_MAX_BLOCKS = TPST_EV_MAX_BLOCKS;  // per matrix: bounds the partial buffer (3 x 128 Fr)
+
+struct Csr3 {
+  const uint32_t* ptr[3];
+  const uint32_t* idx[3];
+  const uint32_t* val[3];
+};
+
+// a 32-byte aligned Fr as two 16-byte loads
+__device__ __forceinline__ Fr load_fr_vec(const uint32_t* p) {
+  const uint4* q = reinterpret_cast<const uint4*>(p);
+  const uint4 a = q[0], b = q[1];
+  Fr r;
+  r.v[0] = a.x, r.v[1] = a.y, r.v[2] = a.z, r.v[3] = a.w;
+  r.v[4] = b.x, r.v[5] = b.y, r.v[6] = b.z, r.v[7] = b.w;
+  return r;
+}
+
+// eq(r, .) from the tables of r's two halves (MSB-first: the high bits of i
+// index the first coordinates): out[i] = hi[i >> lo_bits] * lo[i & (2^lo_bits - 1)]
+// -- one product per entry where k_eq_evals spends ell
+__global__ void k_eq_outer(const uint32_t* __restrict__ hi, const uint32_t* __restrict__ lo, int lo_bits, size_t n,
+                           uint32_t* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const Fr v = mul(load_fr_vec(hi + 8 * (i >> lo_bits)), load_fr_vec(lo + 8 * (i & (((size_t)1 << lo_bits) - 1))));
+  uint4* o = reinterpret_cast<uint4*>(out + 8 * i);
+  o[0] = make_uint4(v.v[0], v.v[1], v.v[2], v.v[3]);
+  o[1] = make_uint4(v.v[4], v.v[5], v.v[6], v.v[7]);
+}
+
+// sum over the 64 lanes of a wave, valid in lane 0 (lanes below `off` always
+// read a partner inside the wave)
+__device__ __forceinline__ Fr wave_sum(Fr a) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    Fr b;
+#pragma unroll
+    for (int k = 0; k < 8; k++) b.v[k] = __shfl_down(a.v[k], off, 64);
+    a = add(a, b);
+  }
+  return a;
+}
+
+// sum over a block of EV_BS threads, valid in thread 0
+__device__ __forceinline__ Fr block_sum(const Fr& a, Fr* sh) {
+  const Fr w = wave_sum(a);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = w;
+  __syncthreads();
+  Fr t = sh[0];
+  if (threadIdx.x == 0)
+    for (int k = 1; k < EV_BS / 64; k++) t = add(t, sh[k]);
+  return t;
+}
+
+// blockIdx.y = matrix; rows in a grid-stride loop, one lane per row:
+// partial[matrix][block] = sum_{rows of the block} eq_rx[row] sum_{e in row} val_e eq_ry[col_e]
+__global__ void __launch_bounds__(EV_BS) k_r1cs_eval(Csr3 m, const uint32_t* __restrict__ eq_rx,
+                                                     const uint32_t* __restrict__ eq_ry, size_t nrows,
+                                                     uint32_t* __restrict__ partial) {
+  __shared__ Fr sh[EV_BS / 64];
+  const unsigned k = blockIdx.y;
+  const uint32_t* __restrict__ ptr = k == 0 ? m.ptr[0] : k == 1 ? m.ptr[1] : m.ptr[2];
+  const uint32_t* __restrict__ idx = k == 0 ? m.idx[0] : k == 1 ? m.idx[1] : m.idx[2];
+  const uint32_t* __restrict__ val = k == 0 ? m.val[0] : k == 1 ? m.val[1] : m.val[2];
+  const size_t stride = (size_t)gridDim.x * EV_BS;
+  Fr acc = Fr::zero();
+  for (size_t r = (size_t)blockIdx.x * EV_BS + threadIdx.x; r < nrows; r += stride) {
+    const uint32_t b = ptr[r], e = ptr[r + 1];
+    if (b == e) continue;
+    Fr row = Fr::zero();
+    for (uint32_t i = b; i < e; i++)
+      row = add(row, mul(load_fr_vec(val + 8 * (size_t)i), load_fr_vec(eq_ry + 8 * (size_t)idx[i])));
+    acc = add(acc, mul(row, load_fr_vec(eq_rx + 8 * r)));
+  }
+  const Fr t = block_sum(acc, sh);
+  if (threadIdx.x == 0) store_f<Fr>(partial + 8 * ((size_t)k * gridDim.x + blockIdx.x), t);
+}
+
+// one block per matrix: out[matrix] = sum of its nblk partials (canonical)
+__global__ void __launch_bounds__(EV_BS) k_r1cs_eval_sum(const uint32_t* __restrict__ partial, unsigned nblk,
+                                                         uint32_t* __restrict__ out) {
+  __shared__ Fr sh[EV_BS / 64];
+  Fr a = Fr::zero();
+  for (unsigned b = threadIdx.x; b < nblk; b += EV_BS)
+    a = add(a, load_fr_vec(partial + 8 * ((size_t)blockIdx.x * nblk + b)));
+  const Fr t = block_sum(a, sh);
+  if (threadIdx.x == 0) store_f<Fr>(out + 8 * (size_t)blockIdx.x, from_mont(t));
+}
+
+// R1CSInstance::is_sat (r1csinstance.rs:244-274): flag any row with Az Bz != Cz
+__global__ void k_sat_flag(const uint32_t* __restrict__ az, const uint32_t* __restrict__ bz,
+                           const uint32_t* __restrict__ cz, size_t nrows, uint32_t* __restrict__ flag) {
+  const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= nrows) return;
+  if (!eq(mul(load_f<Fr>(az + 8 * r), load_f<Fr>(bz + 8 * r)), load_f<Fr>(cz + 8 * r))) atomicOr(flag, 1u);
 }
 
 // ---------------------------------------------- SPARK dense representation --
@@ -751,4 +863,237 @@ extern "C" int tpst_r1cs_commit(tpst_ctx* ctx, tpst_r1cs* R, const uint8_t* labe
     TPST_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   return TPST_OK;
+}
+
+// ================================================== evaluate / verify ====
+int tpst_internal_srs_nv(tpst_ctx* ctx);  // pst_api.hip
+
+// R1CSInstance::evaluate (r1csinstance.rs:308-311): both eq tables and the
+// gather-multiply-reduce on the device; every buffer is allocated before the
+// first launch.
+extern "C" int tpst_r1cs_evaluate(tpst_ctx* ctx, tpst_r1cs* R, const uint64_t* rx, const uint64_t* ry,
+                                  uint64_t* evals) {
+  if (!ctx || !R || !rx || !ry || !evals) return fail(ctx, TPST_E_ARG, "null argument");
+  if (R->owner != ctx) return fail(ctx, TPST_E_ARG, "instance belongs to another context");
+  const int rx_n = log2_exact(R->num_cons), ry_n = log2_exact(R->ncols);
+  std::vector<Fr> pt((size_t)rx_n + ry_n);
+  for (int j = 0; j < rx_n + ry_n; j++) {
+    const uint64_t* c = j < rx_n ? rx + 4 * j : ry + 4 * (j - rx_n);
+    if (!fr_ok_host(c)) return fail(ctx, TPST_E_ARG, "evaluate: coordinate >= r");
+    pt[j] = frc(c);
+  }
+  std::lock_guard<tpst::CtxMutex> lk(ctx->mu);
+  TPST_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const size_t M = R->num_cons, Nz = R->ncols;
+  const unsigned full = grid_for(M, EV_BS);
+  const unsigned nblk = full < EV_MAX_BLOCKS ? full : EV_MAX_BLOCKS;
+  // each eq table is the outer product of the tables of its point's halves
+  const int xl = rx_n / 2, xh = rx_n - xl, yl = ry_n / 2, yh = ry_n - yl;
+  Buf dpt, ex, ey, half[4], partial, dout;
+  TPST_HIP(ctx, dpt.alloc(pt.size() * 32));
+  TPST_HIP(ctx, ex.alloc(M * 32));
+  TPST_HIP(ctx, ey.alloc(Nz * 32));
+  const int hbits[4] = {xh, xl, yh, yl};
+  for (int k = 0; k < 4; k++) TPST_HIP(ctx, half[k].alloc(((size_t)1 << hbits[k]) * 32));
+  TPST_HIP(ctx, partial.alloc((size_t)3 * nblk * 32));
+  TPST_HIP(ctx, dout.alloc(3 * 32));
+  TPST_HIP(ctx, hipMemcpyAsync(dpt.p, pt.data(), pt.size() * 32, hipMemcpyHostToDevice, s));
+  Profiler& pf = ctx->prof;
+  pf.begin(ST_R1CS_EVAL_EQ, s);
+  const int hoff[4] = {0, xh, rx_n, rx_n + yh};  // first coordinate of each half in dpt
+  for (int k = 0; k < 4; k++) {
+    const size_t n = (size_t)1 << hbits[k];
+    k_eq_evals<<<grid_for(n, 256), 256, 0, s>>>(dpt.u() + 8 * (size_t)hoff[k], hbits[k], n, half[k].u());
+  }
+  k_eq_outer<<<grid_for(M, 256), 256, 0, s>>>(half[0].u(), half[1].u(), xl, M, ex.u());
+  k_eq_outer<<<grid_for(Nz, 256), 256, 0, s>>>(half[2].u(), half[3].u(), yl, Nz, ey.u());
+  pf.end(ST_R1CS_EVAL_EQ, s);
+  TPST_HIP(ctx, hipGetLastError());
+  Csr3 csr;
+  for (int m = 0; m < 3; m++) {
+    csr.ptr[m] = R->rptr[m].u();
+    csr.idx[m] = R->ridx[m].u();
+    csr.val[m] = R->rval[m].u();
+  }
+  pf.begin(ST_R1CS_EVAL, s);
+  k_r1cs_eval<<<dim3(nblk, 3), EV_BS, 0, s>>>(csr, ex.u(), ey.u(), M, partial.u());
+  k_r1cs_eval_sum<<<3, EV_BS, 0, s>>>(partial.u(), nblk, dout.u());
+  pf.end(ST_R1CS_EVAL, s);
+  TPST_HIP(ctx, hipGetLastError());
+  TPST_HIP(ctx, hipMemcpyAsync(evals, dout.p, 96, hipMemcpyDeviceToHost, s));
+  TPST_HIP(ctx, hipStreamSynchronize(s));
+  return TPST_OK;
+}
+
+// R1CSInstance::is_sat (r1csinstance.rs:244-274): z = vars || 1 || inputs || 0,
+// Az, Bz, Cz by the prover's kernels, then one flag for any row Az Bz != Cz
+extern "C" int tpst_r1cs_is_sat(tpst_ctx* ctx, tpst_r1cs* R, const uint64_t* vars, const uint64_t* inputs) {
+  if (!ctx || !R || !vars || (R->num_inputs && !inputs)) return fail(ctx, TPST_E_ARG, "null argument");
+  if (R->owner != ctx) return fail(ctx, TPST_E_ARG, "instance belongs to another context");
+  for (size_t i = 0; i < R->num_vars; i++)
+    if (!fr_ok_host(vars + 4 * i)) return fail(ctx, TPST_E_ARG, "witness value >= r");
+  for (size_t i = 0; i < R->num_inputs; i++)
+    if (!fr_ok_host(inputs + 4 * i)) return fail(ctx, TPST_E_ARG, "input value >= r");
+  std::lock_guard<tpst::CtxMutex> lk(ctx->mu);
+  TPST_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const size_t M = R->num_cons, Nz = R->ncols;
+  Buf dvars, dins, z, y[3], flag;
+  TPST_HIP(ctx, dvars.alloc(R->num_vars * 32));
+  TPST_HIP(ctx, dins.alloc(R->num_inputs * 32 + 32));
+  TPST_HIP(ctx, z.alloc(Nz * 32));
+  for (auto& b : y) TPST_HIP(ctx, b.alloc(M * 32));
+  TPST_HIP(ctx, flag.alloc(4));
+  TPST_HIP(ctx, hipMemcpyAsync(dvars.p, vars, R->num_vars * 32, hipMemcpyHostToDevice, s));
+  if (R->num_inputs) TPST_HIP(ctx, hipMemcpyAsync(dins.p, inputs, R->num_inputs * 32, hipMemcpyHostToDevice, s));
+  TPST_HIP(ctx, hipMemsetAsync(flag.p, 0, 4, s));
+  k_make_z<<<grid_for(Nz, 256), 256, 0, s>>>(dvars.u(), R->num_vars, dins.u(), R->num_inputs, Nz, z.u());
+  TPST_HIP(ctx, hipGetLastError());
+  for (int m = 0; m < 3; m++) {
+    k_spmv<<<grid_for(M, 256), 256, 0, s>>>(R->rptr[m].u(), R->ridx[m].u(), R->rval[m].u(), z.u(), M, y[m].u());
+    TPST_HIP(ctx, hipGetLastError());
+  }
+  k_sat_flag<<<grid_for(M, 256), 256, 0, s>>>(y[0].u(), y[1].u(), y[2].u(), M, flag.u());
+  TPST_HIP(ctx, hipGetLastError());
+  uint32_t bad = 0;
+  TPST_HIP(ctx, hipMemcpyAsync(&bad, flag.p, 4, hipMemcpyDeviceToHost, s));
+  TPST_HIP(ctx, hipStreamSynchronize(s));
+  return bad ? fail(ctx, TPST_E_VERIFY, "is_sat: Az * Bz != Cz in some row") : TPST_OK;
+}
+
+// SumcheckInstanceProof::verify (sumcheck.rs:29-66) on the host: NC canonical
+// coefficients per round, constant first, absorbed as sumcheck<> absorbs them.
+// On success `e` is the final claim and rs the derived point.
+static bool sumcheck_verify(const uint64_t* polys, int NC, int rounds, Fr& e, tpst_transcript* tr, Fr* rs) {
+  for (int j = 0; j < rounds; j++) {
+    Fr cs[4];
+    Fr at01 = Fr::zero();  // p(0) + p(1) = 2 c_0 + c_1 + ...
+    for (int c = 0; c < NC; c++) {
+      const uint64_t* w = polys + 4 * ((size_t)j * NC + c);
+      if (!fr_ok_host(w)) return false;
+      cs[c] = frc(w);
+      at01 = add(at01, cs[c]);
+    }
+    at01 = add(at01, cs[0]);
+    if (!eq(at01, e)) return false;
+    for (int c = 0; c < NC; c++) tpst_transcript_append_fr(tr, polys + 4 * ((size_t)j * NC + c));
+    uint64_t rc[4];
+    tpst_transcript_challenge(tr, rc);
+    rs[j] = frc(rc);
+    e = uni_eval(cs, NC, rs[j]);
+  }
+  return true;
+}
+
+// what both verifiers settle before any check of the proof itself
+static int verify_precheck(tpst_ctx* ctx, size_t num_cons, size_t num_vars, size_t num_inputs,
+                           const tpst_r1cs_proof* proof) {
+  if (int rc = r1cs_dims(ctx, num_cons, num_vars, num_inputs)) return rc;
+  const int nvar_bits = log2_exact(num_vars), rx_n = log2_exact(num_cons), ry_n = nvar_bits + 1;
+  if (rx_n > TPST_R1CS_MAX_ROUNDS || ry_n > TPST_R1CS_MAX_ROUNDS || nvar_bits > 2 * TPST_MAX_VARS)
+    return fail(ctx, TPST_E_ARG, "instance too large for tpst_r1cs_proof");
+  if (tpst_internal_srs_nv(ctx) != nvar_bits - nvar_bits / 2)
+    return fail(ctx, TPST_E_STATE, "no SRS loaded for ceil(log2(num_vars) / 2) variables");
+  if (proof->rounds_x != rx_n || proof->rounds_y != ry_n || proof->num_vars_log != nvar_bits ||
+      proof->open.m_col != nvar_bits / 2 || proof->open.m_row != nvar_bits - nvar_bits / 2)
+    return fail(ctx, TPST_E_VERIFY, "proof dimensions do not match the instance");
+  return TPST_OK;
+}
+
+// R1CSVerifierProof::verify as intended (r1csproof.rs:443-486): the checks of
+// R1CSVerificationCircuit::generate_constraints (constraints.rs:263-397) on
+// the host, in the order the prover's transcript saw them, then
+// Polynomial::verify of the witness opening.  r_abc and claims_phase2_z_abc
+// are never read.
+extern "C" int tpst_r1cs_verify_evals(tpst_ctx* ctx, size_t num_cons, size_t num_vars, const uint64_t* inputs,
+                                      size_t num_inputs, const uint64_t* evals, tpst_transcript* tr,
+                                      const tpst_r1cs_proof* proof) {
+  if (!ctx || (num_inputs && !inputs) || !evals || !tr || !proof) return fail(ctx, TPST_E_ARG, "null argument");
+  if (int rc = verify_precheck(ctx, num_cons, num_vars, num_inputs, proof)) return rc;
+  const int rx_n = proof->rounds_x, ry_n = proof->rounds_y, nvar_bits = proof->num_vars_log;
+  const auto bad = [&](const char* what) { return fail(ctx, TPST_E_VERIFY, std::string("r1cs verify: ") + what); };
+  for (size_t i = 0; i < num_inputs; i++)
+    if (!fr_ok_host(inputs + 4 * i)) return bad("input >= r");
+  for (int k = 0; k < 3; k++)
+    if (!fr_ok_host(evals + 4 * k)) return bad("matrix evaluation >= r");
+  // 1. the commitment's transcript state, then the inputs (r1csproof.rs:251-262)
+  uint64_t c[4];
+  tpst_transcript_append_gt(tr, proof->T);
+  tpst_transcript_challenge(tr, c);
+  if (memcmp(c, proof->initial_state, 32) != 0) return bad("initial transcript state");
+  tpst_transcript_reset_fr(tr, proof->initial_state);
+  for (size_t i = 0; i < num_inputs; i++) tpst_transcript_append_fr(tr, inputs + 4 * i);
+  // 2. tau
+  std::vector<Fr> tau(rx_n), rx(rx_n), ry(ry_n);
+  for (int j = 0; j < rx_n; j++) {
+    tpst_transcript_challenge(tr, c);
+    tau[j] = frc(c);
+  }
+  // 3.-4. phase one (degree 3, claim 0); the derived rx is the proof's (constraints.rs:317-319)
+  Fr e1 = Fr::zero();
+  if (!sumcheck_verify(&proof->sc1[0][0][0], 4, rx_n, e1, tr, rx.data())) return bad("phase-one sum-check round");
+  for (int j = 0; j < rx_n; j++) {
+    uint64_t w[4];
+    fro(rx[j], w);
+    if (memcmp(w, proof->rx[j], 32) != 0) return bad("rx");
+  }
+  // 5. the phase-one final claim (constraints.rs:328-340)
+  Fr cl[4];
+  for (int k = 0; k < 4; k++) {
+    if (!fr_ok_host(proof->claims_phase2[k])) return bad("claim >= r");
+    cl[k] = frc(proof->claims_phase2[k]);
+  }
+  if (!eq(cl[3], mul(cl[0], cl[1]))) return bad("claims_phase2[3] != Az Bz");
+  Fr tb = Fr::one();
+  for (int j = 0; j < rx_n; j++)
+    tb = mul(tb, add(mul(tau[j], rx[j]), mul(sub(Fr::one(), tau[j]), sub(Fr::one(), rx[j]))));
+  if (!eq(e1, mul(sub(cl[3], cl[2]), tb))) return bad("phase-one final claim");
+  // 6.-7. phase two (degree 2) on r_A Az + r_B Bz + r_C Cz
+  Fr rabc[3];
+  for (int k = 0; k < 3; k++) {
+    tpst_transcript_challenge(tr, c);
+    rabc[k] = frc(c);
+  }
+  Fr e2 = add(add(mul(rabc[0], cl[0]), mul(rabc[1], cl[1])), mul(rabc[2], cl[2]));
+  if (!sumcheck_verify(&proof->sc2[0][0][0], 3, ry_n, e2, tr, ry.data())) return bad("phase-two sum-check round");
+  for (int j = 0; j < ry_n; j++) {
+    uint64_t w[4];
+    fro(ry[j], w);
+    if (memcmp(w, proof->ry[j], 32) != 0) return bad("ry");
+  }
+  // 8. z(ry) from the witness evaluation and the sparse (1, inputs)
+  //    polynomial (r1csproof.rs:390-398), against the matrix evaluations (:376-388)
+  if (!fr_ok_host(proof->eval_vars_at_ry)) return bad("eval_vars_at_ry >= r");
+  Fr io = Fr::zero();
+  for (size_t i = 0; i <= num_inputs; i++) {
+    Fr chi = Fr::one();
+    for (int j = 0; j < nvar_bits; j++)
+      chi = mul(chi, ((i >> (nvar_bits - 1 - j)) & 1) ? ry[1 + j] : sub(Fr::one(), ry[1 + j]));
+    io = add(io, i ? mul(chi, frc(inputs + 4 * (i - 1))) : chi);
+  }
+  const Fr zry = add(mul(sub(Fr::one(), ry[0]), frc(proof->eval_vars_at_ry)), mul(ry[0], io));
+  const Fr abc = add(add(mul(rabc[0], frc(evals)), mul(rabc[1], frc(evals + 4))), mul(rabc[2], frc(evals + 8)));
+  if (!eq(e2, mul(zry, abc))) return bad("phase-two final claim");
+  // 9. the transcript state after the sum-checks (:389-395)
+  tpst_transcript_challenge(tr, c);
+  if (memcmp(c, proof->transcript_sat_state, 32) != 0) return bad("transcript state after the sum-checks");
+  tpst_transcript_reset_fr(tr, proof->transcript_sat_state);
+  // 10. Polynomial::verify of the witness opening at ry[1..] (:469-480)
+  return tpst_pst_verify(ctx, tr, nvar_bits, &proof->ry[1][0], proof->eval_vars_at_ry, proof->T, &proof->open);
+}
+
+// TestudoNizk::verify (testudo_nizk.rs:136-157) minus the digest append
+extern "C" int tpst_r1cs_verify(tpst_ctx* ctx, tpst_r1cs* R, const uint64_t* inputs, tpst_transcript* tr,
+                                const tpst_r1cs_proof* proof) {
+  if (!ctx || !R || (R->num_inputs && !inputs) || !tr || !proof) return fail(ctx, TPST_E_ARG, "null argument");
+  if (R->owner != ctx) return fail(ctx, TPST_E_ARG, "instance belongs to another context");
+  if (int rc = verify_precheck(ctx, R->num_cons, R->num_vars, R->num_inputs, proof)) return rc;
+  for (int j = 0; j < proof->rounds_x; j++)
+    if (!fr_ok_host(proof->rx[j])) return fail(ctx, TPST_E_VERIFY, "r1cs verify: rx >= r");
+  for (int j = 0; j < proof->rounds_y; j++)
+    if (!fr_ok_host(proof->ry[j])) return fail(ctx, TPST_E_VERIFY, "r1cs verify: ry >= r");
+  uint64_t evals[12];
+  if (int rc = tpst_r1cs_evaluate(ctx, R, &proof->rx[0][0], &proof->ry[0][0], evals)) return rc;
+  return tpst_r1cs_verify_evals(ctx, R->num_cons, R->num_vars, inputs, R->num_inputs, evals, tr, proof);
 }

@@ -109,7 +109,9 @@ class Context:
     # ------------------------------------------------------- profiling ---
     STAGES = ("decompose", "sort", "bounds", "bucket_acc", "reduce", "combine", "batch_sort",
               # sqrt-PST stages under the reference's Timer labels (sqrt_pst.rs:33-262), device spans
-              "build_q", "sqrt_commit", "comm_list", "ipp", "sqrt_open", "msm", "mipp_prove", "pst_open")
+              "build_q", "sqrt_commit", "comm_list", "ipp", "sqrt_open", "msm", "mipp_prove", "pst_open",
+              # tpst_r1cs_evaluate: the two eq tables; the reduction kernel and its partial sum
+              "r1cs_eval_eq", "r1cs_eval")
 
     def profile(self, on: bool):
         self.check(self.lib.tpst_profile_enable(self.h, 1 if on else 0), "tpst_profile_enable")

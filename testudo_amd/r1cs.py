@@ -1,10 +1,13 @@
-"""Spartan R1CS prover around the sqrt-PST commitment (csrc/r1cs.hip through
-the C-ABI): the mirror of R1CSInstance / R1CSProof::prove (r1csinstance.rs,
-r1csproof.rs:237-370), without the Groth16 `prove_verifier` step.
+"""Spartan R1CS prover and verifier around the sqrt-PST commitment
+(csrc/r1cs.hip through the C-ABI): the mirror of R1CSInstance /
+R1CSProof::prove (r1csinstance.rs, r1csproof.rs:237-370), without the Groth16
+`prove_verifier` step, and of the checks its verifier circuit enforces
+(constraints.rs:263-397) run natively.
 
     inst, vars, inputs = R1CSInstance.produce_synthetic_r1cs(ctx, num_cons, num_vars, num_inputs, seed)
     sqrt_pst.srs_setup(ctx, (log2(num_vars) + 1) // 2, seed)
     proof, rx, ry = R1CSProof.prove(inst, vars, inputs, PoseidonTranscript())
+    assert proof.verify(inst, inputs, PoseidonTranscript())
 
 No CPU fallback: every table and sum-check round runs on the device.
 """
@@ -18,7 +21,9 @@ import numpy as np
 from . import _lib
 from .encoding import ptr
 from .engine import Context
-from .sqrt_pst import MippProof, PoseidonTranscript, _unpack
+from .sqrt_pst import MippProof, PoseidonTranscript, _unpack, pack_proof
+
+_E_VERIFY = -5
 
 
 def _fr(a, n=None):
@@ -116,6 +121,29 @@ class R1CSInstance:
                                            ptr(mem), C.byref(n_mem)), "tpst_r1cs_commit")
         return ops, mem
 
+    def evaluate(self, rx, ry) -> np.ndarray:
+        """R1CSInstance::evaluate (r1csinstance.rs:308-311): (A, B, C)(rx, ry) as
+        (3, 4) canonical limbs; rx / ry MSB-first, log2(num_cons) and
+        log2(2 num_vars) coordinates."""
+        rx = _fr(rx, self.num_cons.bit_length() - 1)
+        ry = _fr(ry, self.num_vars.bit_length())
+        out = np.zeros((3, 4), dtype=np.uint64)
+        self.ctx.check(self.ctx.lib.tpst_r1cs_evaluate(self.ctx.h, self.h, ptr(rx), ptr(ry), ptr(out)),
+                       "tpst_r1cs_evaluate")
+        return out
+
+    def _inputs(self, inputs):
+        return _fr(inputs, self.num_inputs) if self.num_inputs else np.zeros((1, 4), dtype=np.uint64)
+
+    def is_sat(self, vars_, inputs) -> bool:
+        """R1CSInstance::is_sat (r1csinstance.rs:244-274)."""
+        rc = self.ctx.lib.tpst_r1cs_is_sat(self.ctx.h, self.h, ptr(_fr(vars_, self.num_vars)),
+                                           ptr(self._inputs(inputs)))
+        if rc == _E_VERIFY:
+            return False
+        self.ctx.check(rc, "tpst_r1cs_is_sat")
+        return True
+
     def __del__(self):
         try:
             if self.h:
@@ -161,3 +189,44 @@ class R1CSProof:
                           eval_vars_at_ry=a(pr.eval_vars_at_ry), comm=U, proof_eval_vars_at_ry=pst,
                           mipp_proof=mipp)
         return proof, proof.rx, proof.ry
+
+    def pack(self) -> "_lib.R1CSProof":
+        """The tpst_r1cs_proof of this proof (the inverse of what prove unpacks)."""
+        pr = _lib.R1CSProof()
+        rxn, ryn = len(self.rx), len(self.ry)
+        n = ryn - 1
+        pr.rounds_x, pr.rounds_y, pr.num_vars_log = rxn, ryn, n
+        w = np.ctypeslib.as_array
+        w(pr.T)[:] = np.asarray(self.T, dtype=np.uint64).reshape(72)
+        w(pr.initial_state)[:] = _fr(self.initial_state, 1)[0]
+        w(pr.sc1)[:rxn] = np.asarray(self.sc_proof_phase1, dtype=np.uint64).reshape(rxn, 4, 4)
+        w(pr.claims_phase2)[:] = _fr(self.claims_phase2, 4)
+        w(pr.sc2)[:ryn] = np.asarray(self.sc_proof_phase2, dtype=np.uint64).reshape(ryn, 3, 4)
+        w(pr.claims_phase2_z_abc)[:] = _fr(self.claims_z_abc, 2)
+        w(pr.r_abc)[:] = _fr(self.r_abc, 3)
+        w(pr.rx)[:rxn] = _fr(self.rx, rxn)
+        w(pr.ry)[:ryn] = _fr(self.ry, ryn)
+        w(pr.transcript_sat_state)[:] = _fr(self.transcript_sat_state, 1)[0]
+        w(pr.eval_vars_at_ry)[:] = _fr(self.eval_vars_at_ry, 1)[0]
+        pr.open = pack_proof(n, self.comm, self.proof_eval_vars_at_ry, self.mipp_proof)
+        return pr
+
+    def verify(self, inst: R1CSInstance, inputs, transcript: PoseidonTranscript, evals=None) -> bool:
+        """TestudoNizk::verify (testudo_nizk.rs:136-157) minus the digest append:
+        R1CSInstance::evaluate at (rx, ry) on the device, the verifier circuit's
+        checks (constraints.rs:263-397) natively, Polynomial::verify of the
+        witness opening.  With ``evals`` = (A, B, C)(rx, ry) given (SNARK mode)
+        the evaluation is the caller's.  False if the proof does not verify;
+        any other failure raises."""
+        ctx = inst.ctx
+        pr = self.pack()
+        ins = inst._inputs(inputs)
+        if evals is None:
+            rc = ctx.lib.tpst_r1cs_verify(ctx.h, inst.h, ptr(ins), C.byref(transcript.t), C.byref(pr))
+        else:
+            rc = ctx.lib.tpst_r1cs_verify_evals(ctx.h, inst.num_cons, inst.num_vars, ptr(ins), inst.num_inputs,
+                                                ptr(_fr(evals, 3)), C.byref(transcript.t), C.byref(pr))
+        if rc == _E_VERIFY:
+            return False
+        ctx.check(rc, "tpst_r1cs_verify")
+        return True
