@@ -403,10 +403,11 @@ def test_srs_setup_matches_oracle(ctx):
         assert np.array_equal(S.srs_export(ctx, nv), orc.SRS(nv, 0x7E57D1).export())
 
 
-@pytest.mark.parametrize("n", [10, 11])
+@pytest.mark.parametrize("n", [10, 11, 16, 17])
 def test_sqrt_pst_vs_cpu_oracle(ctx, n):
-    """benches/pst.rs-shaped config 1 (n = 10) and an odd size, full proof
-    against the C++ oracle."""
+    """benches/pst.rs-shaped config 1 (n = 10) and an odd size, then the
+    smallest size whose opening rebases its a-side (n = 16: m_col = 8, rebase
+    in round 4) and its odd sibling; full proof against the C++ oracle."""
     from testudo_amd import sqrt_pst as S
     nv = (n + 1) // 2
     S.srs_setup(ctx, nv, 0x7E57D1)

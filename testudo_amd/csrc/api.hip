@@ -1,6 +1,7 @@
 // C-ABI entry points (include/tpst.h): context management, device
 // primitives (MSM, multi-pairing, generator multiples) and the field
-// microbenchmark.  The sqrt-PST protocol entry points live in pst_api.hip.
+// microbenchmark.  The sqrt-PST protocol entry points live in pst_api.hip
+// and pst_open.hip (the opening).
 #include <cstring>
 #include "../../include/tpst.h"
 #include "ctx.h"
@@ -46,7 +47,7 @@ extern "C" int tpst_create(int device, tpst_ctx** out) {
   }
   c->mu.stream = &c->stream;
   // the library stream carries every critical path (the opening's transcript
-  // chain in particular); the opening's side streams (pst_api.hip) are
+  // chain in particular); the opening's side streams (pst_open.hip) are
   // created at the lowest priority so the dispatcher favours this one
   int least = 0, greatest = 0;
   if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) greatest = 0;
@@ -260,7 +261,7 @@ static int msm_dev_impl(tpst_ctx* ctx, const void* d_bases, const void* d_scalar
   if (!ctx->msm_tail) {
     int least = 0, greatest = 0;
     TPST_HIP(ctx, hipDeviceGetStreamPriorityRange(&least, &greatest));
-    for (int i = 0; i < 2; i++)  // as pst_api.hip open_streams creates them
+    for (int i = 0; i < 2; i++)  // as pst_open.hip open_streams creates them
       if (!ctx->side[i]) TPST_HIP(ctx, hipStreamCreateWithPriority(&ctx->side[i], hipStreamNonBlocking, least));
     TPST_HIP(ctx, hipStreamCreateWithPriority(&ctx->msm_tail, hipStreamNonBlocking, greatest));
     for (int i = 0; i < tpst_ctx::MSM_SLOTS; i++) {

@@ -56,7 +56,7 @@ struct tpst_ctx {
   tpst::Arena io;      // staging for host-pointer entry points
   tpst::Arena arena2;  // scratch for nested primitives (open / MIPP)
   tpst::Profiler prof; // stage timing (tpst_profile_*)
-  // the opening runs four streams concurrently (pst_api.hip tpst_poly_open):
+  // the opening runs four streams concurrently (pst_open.hip tpst_poly_open):
   // `stream` + side[0..2], each with its own scratch arena; created on first use
   hipStream_t side[3] = {nullptr, nullptr, nullptr};
   tpst::Arena arena_side[3];

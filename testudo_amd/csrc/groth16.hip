@@ -282,13 +282,13 @@ struct tpst_groth16_pk {
   int lg = 0;
   size_t nC = 0;      // C-MSM length: nv + (n - 1) + 3
   Fr vinv;            // 1 / (g^n - 1)
-  Buf twf, twi;       // w^k, w^-k (k < n/2)
-  Buf cosf, cosi;     // n^-1 g^i, n^-1 g^-i
-  Buf bA, bB1, bB2, bC;  // MSM bases (affine, Montgomery) with the constant points appended
-  Buf gamma_abc;      // ni + 1 G1 points (Montgomery)
-  Buf vk;             // alpha_g1 | beta_g2 | gamma_g2 | delta_g2 (Montgomery)
+  DevBuf twf, twi;    // w^k, w^-k (k < n/2)
+  DevBuf cosf, cosi;  // n^-1 g^i, n^-1 g^-i
+  DevBuf bA, bB1, bB2, bC;  // MSM bases (affine, Montgomery) with the constant points appended
+  DevBuf gamma_abc;   // ni + 1 G1 points (Montgomery)
+  DevBuf vk;          // alpha_g1 | beta_g2 | gamma_g2 | delta_g2 (Montgomery)
   // prove-time scratch
-  Buf a, b, c, zm, sA, sB, sC, in, out_x, out_aff;
+  DevBuf a, b, c, zm, sA, sB, sC, in, out_x, out_aff;
   // the G2 MSM runs on its own stream + scratch arena, beside the G1 MSMs
   Arena ar2;
   hipStream_t s2 = nullptr;
@@ -326,7 +326,7 @@ extern "C" int tpst_groth16_setup(tpst_ctx* ctx, tpst_r1cs* R, const uint64_t* t
   if (R->owner != ctx) return setup_fail(ctx, "instance belongs to another context");
   *out = nullptr;
   for (int k = 0; k < 5; k++) {
-    if (!fr_ok_host(toxic + 4 * k)) return setup_fail(ctx, "toxic waste value >= r");
+    if (!fr_ok(toxic + 4 * k)) return setup_fail(ctx, "toxic waste value >= r");
     const uint64_t* t = toxic + 4 * k;
     if (!(t[0] | t[1] | t[2] | t[3])) return setup_fail(ctx, "toxic waste value is zero");
   }
@@ -347,10 +347,10 @@ extern "C" int tpst_groth16_setup(tpst_ctx* ctx, tpst_r1cs* R, const uint64_t* t
   const size_t n = P->n = (size_t)1 << P->lg;
   P->nC = P->nv + (n - 1) + 3;
   if (P->nC > MSM_MAX_POINTS) return setup_fail(ctx, "instance too large");
-  const Fr tau = frc(toxic), alpha = frc(toxic + 4), beta = frc(toxic + 8), gamma = frc(toxic + 12),
-           delta = frc(toxic + 16);
+  const Fr tau = fr_canon(toxic), alpha = fr_canon(toxic + 4), beta = fr_canon(toxic + 8),
+           gamma = fr_canon(toxic + 12), delta = fr_canon(toxic + 16);
   // domain constants
-  Fr omega = frc(FR_ROOT47);
+  Fr omega = fr_canon(FR_ROOT47);
   for (int k = P->lg; k < FR_TWO_ADICITY; k++) omega = mul(omega, omega);
   const Fr omega_inv = inv(omega), n_inv = inv(fr_u64(n)), g = fr_u64(FR_GENERATOR), g_inv = inv(g);
   P->vinv = inv(sub(fr_pow_host(g, n), Fr::one()));
@@ -368,11 +368,11 @@ extern "C" int tpst_groth16_setup(tpst_ctx* ctx, tpst_r1cs* R, const uint64_t* t
   k_pow_table<<<grid_for(n, 256), 256, 0, s>>>(arg(g_inv), arg(n_inv), n, P->cosi.u());
   TPST_HIP(ctx, hipGetLastError());
   // a, b, c at tau per variable
-  Buf u, at, bt, ct, sc;
+  DevBuf u, at, bt, ct, sc;
   TPST_HIP(ctx, u.alloc(n * 32));
   k_lagrange<<<grid_for(n, 256), 256, 0, s>>>(arg(tau), arg(omega), arg(mul(zt, n_inv)), n, u.u());
   TPST_HIP(ctx, hipGetLastError());
-  Buf* tabs[3] = {&at, &bt, &ct};
+  DevBuf* tabs[3] = {&at, &bt, &ct};
   for (int m = 0; m < 3; m++) {
     TPST_HIP(ctx, tabs[m]->alloc(P->ncols * 32));
     k_cols<<<grid_for(P->ncols, 256), 256, 0, s>>>(R->cptr[m].u(), R->cidx[m].u(), R->cval[m].u(), u.u(), P->ncols,
@@ -467,7 +467,7 @@ extern "C" int tpst_groth16_vk(tpst_ctx* ctx, const tpst_groth16_pk* pk, uint64_
   std::lock_guard<tpst::CtxMutex> lk(ctx->mu);
   TPST_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  Buf o;
+  DevBuf o;
   const size_t ng = pk->ni + 1;
   TPST_HIP(ctx, o.alloc(96 + 3 * 192 + ng * 96));
   TPST_HIP(ctx, affine_from_mont<Fq>(s, pk->vk.u(), o.u(), 1));
@@ -516,9 +516,9 @@ static int check_inputs(tpst_ctx* ctx, const tpst_groth16_pk* P, const tpst_r1cs
   if (R->num_cons != P->num_cons || R->num_vars != P->nv || R->num_inputs != P->ni)
     return fail(ctx, TPST_E_ARG, "proving key does not match the instance");
   for (size_t i = 0; i < P->nv; i++)
-    if (!fr_ok_host(vars + 4 * i)) return fail(ctx, TPST_E_ARG, "witness value >= r");
+    if (!fr_ok(vars + 4 * i)) return fail(ctx, TPST_E_ARG, "witness value >= r");
   for (size_t i = 0; i < P->ni; i++)
-    if (!fr_ok_host(inputs + 4 * i)) return fail(ctx, TPST_E_ARG, "input value >= r");
+    if (!fr_ok(inputs + 4 * i)) return fail(ctx, TPST_E_ARG, "input value >= r");
   return TPST_OK;
 }
 
@@ -552,12 +552,12 @@ extern "C" int tpst_groth16_prove(tpst_ctx* ctx, tpst_groth16_pk* pk, tpst_r1cs*
   if (!ctx || !pk || !R || !vars || (R->num_inputs && !inputs) || !rs || !A || !B || !C)
     return fail(ctx, TPST_E_ARG, "null argument");
   if (int rc = check_inputs(ctx, pk, R, vars, inputs)) return rc;
-  if (!fr_ok_host(rs) || !fr_ok_host(rs + 4)) return fail(ctx, TPST_E_ARG, "r or s >= r");
+  if (!fr_ok(rs) || !fr_ok(rs + 4)) return fail(ctx, TPST_E_ARG, "r or s >= r");
   std::lock_guard<tpst::CtxMutex> lk(ctx->mu);
   TPST_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   tpst_groth16_pk* P = pk;
-  const Fr r = frc(rs), sv = frc(rs + 4);
+  const Fr r = fr_canon(rs), sv = fr_canon(rs + 4);
   if (int rc = upload_assignment(ctx, P, vars, inputs)) return rc;
   // constant terms of each MSM (canonical scalars after the variables)
   const size_t nA = P->nq + 2, tc = P->nv + P->n - 1;
@@ -621,9 +621,6 @@ extern "C" int tpst_groth16_prove(tpst_ctx* ctx, tpst_groth16_pk* pk, tpst_r1cs*
 // Validate::Yes would; then e(A, B) == e(alpha, beta) e(IC, gamma) e(C, delta)
 // with IC = gamma_abc[0] + sum_i inputs_i gamma_abc[i + 1] (device MSM), as one
 // device multi-pairing of (A, B), (-alpha, beta), (-IC, gamma), (-C, delta).
-bool tpst_internal_g1_valid(const uint64_t* p);  // pst_api.hip
-bool tpst_internal_g2_valid(const uint64_t* p);
-
 extern "C" int tpst_groth16_verify(tpst_ctx* ctx, const uint64_t* alpha_g1, const uint64_t* beta_g2,
                                    const uint64_t* gamma_g2, const uint64_t* delta_g2, const uint64_t* gamma_abc_g1,
                                    size_t n_abc, const uint64_t* inputs, size_t n_inputs, const uint64_t* A,
@@ -633,14 +630,14 @@ extern "C" int tpst_groth16_verify(tpst_ctx* ctx, const uint64_t* alpha_g1, cons
     return fail(ctx, TPST_E_ARG, "null argument");
   if (n_abc != n_inputs + 1) return fail(ctx, TPST_E_ARG, "wrong number of public inputs");
   for (size_t i = 0; i < n_inputs; i++)
-    if (!fr_ok_host(inputs + 4 * i)) return fail(ctx, TPST_E_VERIFY, "public input >= r");
-  if (!tpst_internal_g1_valid(A) || !tpst_internal_g2_valid(B) || !tpst_internal_g1_valid(C))
+    if (!fr_ok(inputs + 4 * i)) return fail(ctx, TPST_E_VERIFY, "public input >= r");
+  if (!point_valid<Fq>(A) || !point_valid<Fq2>(B) || !point_valid<Fq>(C))
     return fail(ctx, TPST_E_VERIFY, "malformed proof element");
-  if (!tpst_internal_g1_valid(alpha_g1) || !tpst_internal_g2_valid(beta_g2) || !tpst_internal_g2_valid(gamma_g2) ||
-      !tpst_internal_g2_valid(delta_g2))
+  if (!point_valid<Fq>(alpha_g1) || !point_valid<Fq2>(beta_g2) || !point_valid<Fq2>(gamma_g2) ||
+      !point_valid<Fq2>(delta_g2))
     return fail(ctx, TPST_E_VERIFY, "malformed verifying key");
   for (size_t i = 0; i < n_abc; i++)
-    if (!tpst_internal_g1_valid(gamma_abc_g1 + 12 * i)) return fail(ctx, TPST_E_VERIFY, "malformed verifying key");
+    if (!point_valid<Fq>(gamma_abc_g1 + 12 * i)) return fail(ctx, TPST_E_VERIFY, "malformed verifying key");
   std::vector<uint64_t> sc(4 * n_abc, 0);
   sc[0] = 1;
   if (n_inputs) memcpy(sc.data() + 4, inputs, n_inputs * 32);

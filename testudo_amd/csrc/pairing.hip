@@ -741,7 +741,7 @@ hipError_t multi_pairing_prepared(Arena& ar, hipStream_t s, const uint32_t* d_g1
   return pairing_from_lines(ar, s, lines, groups, n, d_out, final_exp);
 }
 
-// ---- MIPP look-ahead (pst_api.hip tpst_poly_open) --------------------------
+// ---- MIPP look-ahead (pst_open.hip tpst_poly_open) -------------------------
 // The 8 pairing products of round-r vectors (a, h; len, s = len/2, s' = s/2)
 // whose combination with round r's challenge gives round r+1's cross terms:
 //   group  0 A0 (i, i+s')   1 A3 (i+s, i+s+s')   2 A1 (i, i+s+s')   3 A2 (i+s, i+s')
@@ -860,7 +860,7 @@ __device__ bool regs_equal(const wave::lds_t* lds, int a, int b) {
   return __all(same ? 1 : 0) != 0;
 }
 
-// mipp: the opening's look-ahead combination (pst_api.hip): wave i raises
+// mipp: the opening's look-ahead combination (pst_open.hip): wave i raises
 // base[MIPP_POW_SEL[i]] in place (out == base), no membership test (the bases
 // are final-exponentiation outputs)
 __constant__ uint32_t MIPP_POW_SEL[4] = {2, 3, 6, 7};

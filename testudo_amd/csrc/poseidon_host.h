@@ -1,8 +1,8 @@
 // Host-side Poseidon sponge of the Fiat-Shamir transcript
 // (poseidon_transcript.rs; ark-crypto-primitives PoseidonSponge<Fq>) and the
 // 64-bit-limb Montgomery arithmetic it runs on.  Host only: included by
-// pst_api.hip (the transcript C-ABI and the MIPP prover/verifier loops) and by
-// tools/host_poseidon_bench.cpp.
+// pst_api.hip (the transcript C-ABI and the MIPP verifier loop), pst_open.hip
+// (the MIPP prover loop) and by tools/host_poseidon_bench.cpp.
 #pragma once
 #include <cstdint>
 #include <cstring>

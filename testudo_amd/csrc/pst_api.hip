@@ -1,6 +1,8 @@
 // sqrt-PST protocol layer of libtpst (include/tpst.h): SRS (MultilinearPC
-// keys), the Polynomial handle (sqrt_pst.rs:14-265), MIPP prover/verifier
-// (mipp.rs:31-320) and the Poseidon transcript (poseidon_transcript.rs).
+// keys), the Polynomial handle and its commit (sqrt_pst.rs:14-265), the
+// verifier (mipp.rs:182-320), the MultilinearPC calls and the Poseidon
+// transcript (poseidon_transcript.rs).  The opening (Polynomial::open with
+// the MIPP prover) is pst_open.hip; the state both share is pst_state.h.
 //
 // Everything heavy runs on the device (K1 row MSMs, K2 MSMs, K3 G2 MSMs, K4
 // pairings, MIPP folds, Fr kernels); the host keeps the Fiat-Shamir
@@ -9,7 +11,6 @@
 #include <cstring>
 #include <memory>
 #include <vector>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 
@@ -21,113 +22,20 @@
 #include "pst_kernels.h"
 #include "trace.h"
 #include "poseidon_host.h"
+#include "pst_state.h"
 
 using namespace tpst;
 
 // =================================================================== host ==
 namespace {
 
-Fr fr_canon(const uint64_t* c) {
-  Fr a;
-  memcpy(a.v, c, 32);
-  return to_mont(a);
-}
-void fr_out(const Fr& a, uint64_t* c) {
-  Fr r = from_mont(a);
-  memcpy(c, r.v, 32);
-}
-
-// TPST_OPEN_TRACE=1: per-round host timings of tpst_poly_open on stderr
-static double host_us() {
-  return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-static bool open_trace() {
-  static const bool on = getenv("TPST_OPEN_TRACE") != nullptr;
-  return on;
-}
-
-// y > -y on canonical limbs  <=>  2y > p
-bool y_is_negative(const uint64_t* y) {
-  // compare y with p - y
-  uint64_t ny[6];
-  unsigned __int128 br = 0;
-  const uint32_t* p32 = params::FQ_P;
-  for (int i = 0; i < 6; i++) {
-    const uint64_t pi = (uint64_t)p32[2 * i] | ((uint64_t)p32[2 * i + 1] << 32);
-    unsigned __int128 d = (unsigned __int128)pi - y[i] - (uint64_t)br;
-    ny[i] = (uint64_t)d;
-    br = (d >> 64) & 1;
-  }
-  for (int i = 5; i >= 0; i--)
-    if (y[i] != ny[i]) return y[i] > ny[i];
-  return false;
-}
-
-void g1_bytes(const uint64_t* p, uint8_t* b) {  // ark serialize Compress::No
-  bool inf = true;
-  for (int i = 0; i < 12; i++) inf &= p[i] == 0;
-  memcpy(b, p, 96);
-  if (inf)
-    b[95] |= 0x40;
-  else if (y_is_negative(p + 6))
-    b[95] |= 0x80;
-}
-
 // host Fr helpers
 Fr fr_inv(const Fr& a) { return inv(a); }
 
-// device XYZZ points (field.h Montgomery limbs, the same bits as host::HFq)
-// -> canonical affine on the host: the open's few-point outputs (a round's
-// u_l / u_r, U, final_a, final_h) need one inversion each, ~15 us here
-// against a ~0.1 ms single-point kernel on the round's critical stream
-template <class F>
-void xyzz_to_canonical_host(const uint8_t* raw, size_t n, uint64_t* out) {
-  using H = typename host::HostOf<F>::T;
-  constexpr size_t PT = sizeof(Xyzz<F>), NQ = host::HostOf<F>::NQ;
-  static_assert(sizeof(Xyzz<H>) == PT, "host and device XYZZ layouts differ");
-  for (size_t i = 0; i < n; i++) {
-    Xyzz<H> x;
-    memcpy(&x, raw + i * PT, PT);
-    host::aff_put(to_affine(x), out + i * 12 * NQ);
-  }
-}
-
-// base-x digits of a canonical Fr e (e < r < x^4): e = sum_j out[j] x^j, for
-// the GT exponentiations by Frobenius splitting (pairing.hip k_gt_pow_wave)
-void base_x_digits(const uint64_t* e, uint64_t* out) {
-  uint64_t q[4] = {e[0], e[1], e[2], e[3]};
-  for (int t = 0; t < 4; t++) {
-    unsigned __int128 rem = 0;
-    for (int l = 3; l >= 0; l--) {
-      const unsigned __int128 cur = (rem << 64) | q[l];
-      q[l] = (uint64_t)(cur / params::BLS_X);
-      rem = cur % params::BLS_X;
-    }
-    out[t] = (uint64_t)rem;
-  }
-}
-
-// ---- proof-element validation (the reference's elements are typed arkworks
-// values, validated when deserialized; here they arrive as raw limbs) ----
-bool limbs_lt(const uint64_t* a, const uint32_t* mod32, int n64) {
-  for (int i = n64 - 1; i >= 0; i--) {
-    const uint64_t mi = (uint64_t)mod32[2 * i] | ((uint64_t)mod32[2 * i + 1] << 32);
-    if (a[i] != mi) return a[i] < mi;
-  }
-  return false;
-}
-bool fq_ok(const uint64_t* a) { return limbs_lt(a, params::FQ_P, 6); }
-bool fr_ok(const uint64_t* a) { return limbs_lt(a, params::FR_P, 4); }
 bool all_zero(const uint64_t* a, int n) {
   for (int i = 0; i < n; i++)
     if (a[i]) return false;
   return true;
-}
-// canonical coordinates, on the curve, and r * P == O (prime-order subgroup),
-// on 64-bit host arithmetic (host_curve.h)
-template <class F>
-bool point_valid(const uint64_t* p) {
-  return host::point_in_subgroup<F>(p);
 }
 bool gt_ok(const uint64_t* f) {
   for (int k = 0; k < 12; k++)
@@ -135,84 +43,9 @@ bool gt_ok(const uint64_t* f) {
   return true;
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t alloc(size_t b) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = b;
-    return b ? hipMalloc(&p, b) : hipSuccess;
-  }
-  uint32_t* u() const { return (uint32_t*)p; }
-  // grow-only: keep the buffer when it is large enough
-  hipError_t grow(size_t b) { return (p && bytes >= b) ? hipSuccess : alloc(b); }
-};
-
-// the opening's device buffers, kept across openings (grow-only): ~40
-// hipMalloc / hipFree pairs per call cost the host ~0.4 ms
-struct OpenBufs {
-  DevBuf up, A, P, Y, chiC, ScA, ScB, ScC, ScD[2], xa, xb, xd, xh, xp, xl[2], LAo[2], Hb[3], Lb[3], gts, canA, canC,
-      canD, pstA, pstB, Wall, Wiall, SqT[2], SqG[2], SqM, chis_own, tLoc, A1x, A1, tA1, Hbl[3], Lbl[3];
-};
-
 }  // namespace
 
 // ================================================================ state ==
-struct SrsState {
-  int nv = 0;
-  DevBuf g, h;                    // affine Montgomery
-  std::vector<std::unique_ptr<DevBuf>> pg, ph, pg_pair, ph_pair;
-  DevBuf gmask, hmask;
-  BatchTables tables;             // K1 tables over powers_of_g[0]
-  DevBuf hprep[2];                // G2Prepared of powers_of_h[odd], odd = 0/1
-  DevBuf prep_scratch;            // residue lines of the RNS G2 preparation (g2_prepare_scratch)
-  // fixed-base tables (fbt.h), built on first open
-  DevBuf t_pg0;                   // powers_of_g[0]            (U = commit(q))
-  DevBuf t_h[2];                  // powers_of_h[odd]           (MIPP h folds)
-  DevBuf t_pgp, t_php;            // concatenated pg_pair / ph_pair levels (PST level proofs)
-  DevBuf seg;                     // u32 level offsets into the concatenation
-  std::vector<size_t> lvl_off;
-  bool fbt_ready = false, t_h_ready[2] = {false, false};
-  DevBuf t_A;                     // per-opening table over the row commitments
-  size_t t_A_n = 0;
-  // a rank's share of the SRS side for the row-sharded opening (every W-th
-  // point of powers_of_h[odd] from `rank`, its prepared lines and table)
-  struct Local {
-    int W = 0, rank = -1;
-    DevBuf H0, L0, tH;
-  } local[2];
-  // t_A prebuilt by tpst_poly_commit (beside its IPP) for exactly these
-  // canonical row commitments; consumed by the next opening of them
-  std::vector<uint64_t> t_A_key;
-  std::vector<uint64_t> flat;     // canonical export
-  OpenBufs ob;                    // the opening's device buffers (grow-only)
-  ~SrsState() { batch_tables_free(tables); }
-};
-
-struct tpst_poly {
-  tpst_ctx* ctx;
-  int n, m_col, m_row, odd;
-  DevBuf Zown;
-  const uint32_t* d_Z = nullptr;  // canonical Fr
-  // column slice (multi-GPU shard): only columns [col0,
-  // col0 + ncols) of the strided view are resident, as an N x ncols block;
-  // ncols == 0 means the whole polynomial
-  size_t col0 = 0, ncols = 0;
-  DevBuf q, chis;                 // Montgomery
-  bool has_q = false;
-  // opening-only handle (row-sharded commit): q combined from
-  // the ranks' shares, no evaluations resident; optionally c_u combined too
-  bool q_only = false;
-  bool has_u = false;
-  uint64_t U[12] = {};
-};
-
-static int srs_fbt(tpst_ctx* ctx, SrsState* st, int odd);
-
 static std::unique_ptr<SrsState>& srs_slot(tpst_ctx* ctx) {
   static std::mutex mu;
   static std::vector<std::pair<tpst_ctx*, std::unique_ptr<SrsState>>> slots;
@@ -285,10 +118,10 @@ static int srs_install(tpst_ctx* ctx, int nv, const uint64_t* flat) {
   return TPST_OK;
 }
 
-static SrsState* srs_of(tpst_ctx* ctx) { return srs_slot(ctx).get(); }
+SrsState* tpst::srs_of(tpst_ctx* ctx) { return srs_slot(ctx).get(); }
 
-// internal (r1cs.hip): the number of variables of the loaded SRS, or -1
-int tpst_internal_srs_nv(tpst_ctx* ctx) {
+// (r1cs.hip) the number of variables of the loaded SRS, or -1
+int tpst::srs_nv(tpst_ctx* ctx) {
   SrsState* st = srs_of(ctx);
   return st ? st->nv : -1;
 }
@@ -297,7 +130,7 @@ int tpst_internal_srs_nv(tpst_ctx* ctx) {
 // lines, ~53 KB per point) sized for the largest batch prepared since the
 // SRS was installed -- the install's 2^nv batch is released right after it
 // (217 MB at nv = 12); callers size it before enqueueing any stream work
-static int prep_scratch_for(tpst_ctx* ctx, SrsState* st, size_t n) {
+int tpst::prep_scratch_for(tpst_ctx* ctx, SrsState* st, size_t n) {
   const size_t b = g2_prepare_scratch(n);
   if (st->prep_scratch.p && st->prep_scratch.bytes >= b) return TPST_OK;
   TPST_HIP(ctx, st->prep_scratch.alloc(b));  // hipFree of a smaller one waits for its users
@@ -443,15 +276,7 @@ extern "C" int tpst_srs_export(tpst_ctx* ctx, uint64_t* flat) {
 extern "C" int tpst_g1_check(const uint64_t* p) { return p && point_valid<Fq>(p) ? TPST_OK : TPST_E_VERIFY; }
 extern "C" int tpst_g2_check(const uint64_t* p) { return p && point_valid<Fq2>(p) ? TPST_OK : TPST_E_VERIFY; }
 
-// internal (groth16.hip): the same element validation as the PST verifier
-bool tpst_internal_g1_valid(const uint64_t* p) { return point_valid<Fq>(p); }
-bool tpst_internal_g2_valid(const uint64_t* p) { return point_valid<Fq2>(p); }
-
 // ============================================================ transcript ==
-// internal (r1cs.hip): the device copy of a whole polynomial's evaluations
-// (canonical Fr, original order), or nullptr for a column shard
-const uint32_t* tpst_internal_poly_evals(const tpst_poly* p) { return p && !p->ncols ? p->d_Z : nullptr; }
-
 extern "C" void tpst_transcript_init(tpst_transcript* t) {
   if (!t) return;
   memset(t, 0, sizeof *t);
@@ -523,7 +348,7 @@ extern "C" int tpst_transcript_challenge(tpst_transcript* t, uint64_t* out) {
 }
 
 // ================================================================ poly ===
-static int poly_dims(int n, int& m_col, int& m_row, int& odd) {
+int tpst::poly_dims(int n, int& m_col, int& m_row, int& odd) {
   if (n < 2 || n > 40) return -1;
   m_col = n / 2;
   m_row = n - m_col;
@@ -595,7 +420,7 @@ static int poly_need_full(tpst_ctx* ctx, const tpst_poly* p) {
 
 // eval / open need q and chi(b): a whole polynomial computes them, an
 // opening-only handle carries them
-static int poly_need_q_source(tpst_ctx* ctx, const tpst_poly* p) {
+int tpst::poly_need_q_source(tpst_ctx* ctx, const tpst_poly* p) {
   return p->q_only ? TPST_OK : poly_need_full(ctx, p);
 }
 
@@ -613,7 +438,7 @@ extern "C" int tpst_poly_from_evaluations_dev(tpst_ctx* ctx, const void* d_Z, in
 extern "C" void tpst_poly_free(tpst_poly* p) { delete p; }
 
 // get_q (sqrt_pst.rs:81-101): chis over b = point[m_row..], q = Z^T chis
-static int poly_get_q(tpst_ctx* ctx, tpst_poly* p, const uint64_t* point) {
+int tpst::poly_get_q(tpst_ctx* ctx, tpst_poly* p, const uint64_t* point) {
   TraceRange tr("build_q");
   hipStream_t s = ctx->stream;
   ctx->prof.begin(ST_BUILD_Q, s);
@@ -658,11 +483,10 @@ extern "C" int tpst_poly_eval(tpst_ctx* ctx, tpst_poly* p, const uint64_t* point
 }
 
 // commit (sqrt_pst.rs:117-149): K1 row MSMs + IPP T = prod e(C_i, h_i)
-static int open_streams(tpst_ctx* ctx, size_t n_events, size_t pinned_bytes, bool comm = false);
 
 // the context's pinned host staging (grow-only; the opening's per-round
 // transfers, the commit's outputs)
-static int ensure_pinned(tpst_ctx* ctx, size_t bytes) {
+int tpst::ensure_pinned(tpst_ctx* ctx, size_t bytes) {
   if (ctx->pinned_cap >= bytes) return TPST_OK;
   if (ctx->pinned) TPST_HIP(ctx, hipHostFree(ctx->pinned));
   ctx->pinned = nullptr;
@@ -940,7 +764,7 @@ extern "C" int tpst_gt_final_exp_product_dev(tpst_ctx* ctx, const void* d_partia
 // and of c_u = MSM(comm_list, chi(b))                      (sqrt_pst.rs:198);
 // the shares are gathered as bytes (RCCL has no mod-r or elliptic-curve
 // reduction) and summed on rank 0, which then opens from q alone.
-static int chi_b_table(tpst_ctx* ctx, int m_col, int m_row, const uint64_t* point, DevBuf& chis) {
+int tpst::chi_b_table(tpst_ctx* ctx, int m_col, int m_row, const uint64_t* point, DevBuf& chis) {
   hipStream_t s = ctx->stream;
   DevBuf b;
   TPST_HIP(ctx, b.alloc((size_t)(m_col ? m_col : 1) * 32));
@@ -1060,16 +884,9 @@ extern "C" int tpst_poly_from_q_dev(tpst_ctx* ctx, int n, const uint64_t* point,
   return TPST_OK;
 }
 
-// --------------------------------------------------------------- open ----
-// The opening is latency-bound (transcript rounds of small MSMs and pairings),
-// so every MSM of it runs on fixed-base lookup tables (fbt.h): the SRS sides
-// are tabulated once per SRS, the row commitments once per opening, and each
-// MIPP round's folds / cross terms are grouped MSMs over the ORIGINAL bases
-// with scalars that are products of the challenges so far.
-
 // tabulate the SRS (fbt.h) for opening polynomials of parity `odd` (at SRS
 // install; the open path re-checks and is a no-op then)
-static int srs_fbt(tpst_ctx* ctx, SrsState* st, int odd) {
+int tpst::srs_fbt(tpst_ctx* ctx, SrsState* st, int odd) {
   hipStream_t s = ctx->stream;
   const int nv = st->nv;
   if (!st->fbt_ready) {
@@ -1101,918 +918,6 @@ static int srs_fbt(tpst_ctx* ctx, SrsState* st, int odd) {
     st->t_h_ready[odd] = true;
   }
   return TPST_OK;
-}
-
-// PST open of 2^k evals (Montgomery) at k Montgomery
-// scalars d_pt over the pair levels off..off+k-1: the k quotient scalar
-// vectors first (cheap Fr recurrence), then ONE grouped table MSM with a
-// group per level.  Writes k XYZZ points.  Stream-ordered on `s` with the
-// caller's scratch (pst_open_scratch_words u32), so it can run beside the MIPP.
-static size_t pst_open_scratch_words(const SrsState* st, int k) {
-  return ((size_t)2 << k) * 8 + st->lvl_off[st->nv] * 8;
-}
-
-template <class F>
-static hipError_t pst_open_fbt_s(hipStream_t s, Arena& ar, const SrsState* st, const uint32_t* table, int off,
-                                 const uint32_t* d_evals, int k, const uint32_t* d_pt, Xyzz<F>* d_out,
-                                 uint32_t* scratch) {
-  const size_t full = (size_t)1 << k;
-  uint32_t* cur = scratch;
-  uint32_t* nxt = scratch + full * 8;
-  uint32_t* sc = scratch + 2 * full * 8;
-  hipError_t e = hipMemcpyAsync(cur, d_evals, full * 32, hipMemcpyDeviceToDevice, s);
-  if (e != hipSuccess) return e;
-  for (int i = 0; i < k; i++) {
-    const size_t half = (size_t)1 << (k - i - 1);
-    e = pst_step(s, cur, half, d_pt + 8 * i, sc + 8 * st->lvl_off[off + i], nxt);
-    if (e != hipSuccess) return e;
-    std::swap(cur, nxt);
-  }
-  FbGroups g;
-  g.groups = k;
-  g.members = (size_t)1 << (k - 1);
-  g.d_seg = st->seg.u() + off;
-  return fbt_msm<F>(ar, s, table, sc, g, d_out);
-}
-
-template <class F>
-static int pst_open_fbt(tpst_ctx* ctx, SrsState* st, const uint32_t* table, int off, const uint32_t* d_evals, int k,
-                        const uint32_t* d_pt, Xyzz<F>* d_out) {
-  DevBuf scratch;
-  TPST_HIP(ctx, scratch.alloc(pst_open_scratch_words(st, k) * 4));
-  TPST_HIP(ctx, pst_open_fbt_s<F>(ctx->stream, ctx->arena, st, table, off, d_evals, k, d_pt, d_out, scratch.u()));
-  return TPST_OK;
-}
-
-// ---------------------------------------------------------------- open ----
-// Streams of the opening (created once per context) and a pool of events.
-static int open_streams(tpst_ctx* ctx, size_t n_events, size_t pinned_bytes, bool comm) {
-  int least = 0, greatest = 0;
-  TPST_HIP(ctx, hipDeviceGetStreamPriorityRange(&least, &greatest));
-  // side streams at the least priority (the look-ahead streams at the
-  // greatest won an open-only sweep, 14.2 -> 13.8 ms, but lost in the commit +
-  // open bench: 2^20 open 12.3 -> 13.9 ms; profiles/r04/late/prio6_bench*.json)
-  for (int i = 0; i < 3; i++)
-    if (!ctx->side[i]) TPST_HIP(ctx, hipStreamCreateWithPriority(&ctx->side[i], hipStreamNonBlocking, least));
-  // the row-sharded opening's collectives, in one issue order on every rank
-  if (comm && !ctx->comm) TPST_HIP(ctx, hipStreamCreateWithPriority(&ctx->comm, hipStreamNonBlocking, greatest));
-  // the per-round h preparation of the opening (its own hardware queue: on
-  // stream A it delayed the next round's t; 2^20 open 13.0 -> 11.4 ms; at
-  // the least priority 11.05 -> 11.30 ms, profiles/r06/ab/ab_open_c_prio.txt)
-  if (!ctx->side_c) TPST_HIP(ctx, hipStreamCreateWithPriority(&ctx->side_c, hipStreamNonBlocking, greatest));
-  while (ctx->events.size() < n_events) {
-    hipEvent_t e;
-    TPST_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    ctx->events.push_back(e);
-  }
-  return ensure_pinned(ctx, pinned_bytes);
-}
-
-// Polynomial::open (sqrt_pst.rs:168-230) with MippProof::prove (mipp.rs:31-153).
-//
-// Critical path = the transcript: each MIPP round's challenge needs that
-// round's comms_u and comms_t, and the next round's folds need the challenge.
-// Per round r (len = C >> r, s = len / 2, s' = s / 2) the work is spread
-// over 4 streams (one hardware queue each; A at the highest priority):
-//   A (critical): t^(r) = (t_l, t_r).  Round 0 pairs the row commitments
-//     directly.  From round 1 on, t^(r) comes out of the LOOK-AHEAD of round
-//     r-1 (stream D): with a' = a_L + c a_R, h' = h_L + c^-1 h_R (mipp.rs:101-
-//     120) bilinearity splits round r's cross products into eight pairing
-//     products of round r-1's vectors that do not involve c = c_{r-1},
-//       t_l = A0 A3 A1^(c^-1) A2^c,  t_r = B0 B3 B1^(c^-1) B2^c
-//     (pairing.hip, mipp_lookahead), so once c is known the critical path is
-//     four GT exponentiations (base-x Frobenius splitting, ~0.7 ms) and two
-//     products instead of fold + Miller loops + final exponentiations
-//     (~3.3 ms); comms_t -> host.
-//   D: the look-ahead of round r for round r+1: a^(r) and c'a^(r) as ONE
-//     grouped table MSM over the original row commitments (scalar sets W,
-//     c'W: a^(r)_i = sum_t W_t a_{i+t len}, c' = the previous challenge
-//     inverse), then the 8 products against the PREVIOUS round's prepared h:
-//       e(a_i, h^(r)_k) = e(a_i, h^(r-1)_k) e(c' a_i, h^(r-1)_{k+len})
-//     -> Miller loops + 8 final exponentiations, overlapping round r's own
-//     transcript work.
-//   B: y fold (compress_field, mipp.rs:124-136) and the cross MSMs u_l, u_r
-//     (mipp.rs:66-75) -> canonical -> host; in round 0 first U =
-//     MSM(comm_list, chi(b)) (sqrt_pst.rs:198) and after it the PST proof of
-//     q (sqrt_pst.rs:218-225), which needs nothing from the MIPP.
-//   C: in round 0 the fold table over comm_list (fbt.h); then h^(r) =
-//     sum_t Wi_t h_{i + t len} (table MSM over powers_of_h) -> affine ->
-//     G2Prepared, consumed by the look-ahead of round r+1.
-// The host waits only for the round's comms (pinned staging), absorbs them
-// (mipp.rs:97-101) and squeezes the challenge; no stream is drained mid-open.
-//
-// Row-sharded form (sh != nullptr, tpst_poly_open_sharded):
-// rank g of W owns the rows i = g mod W of comm_list, h and y.  While
-// len >= 4W every fold group (a^(r)_i = sum_t W_t a_{i + t len}) lies on one
-// rank (i + t len = i mod W), and so does every look-ahead pair (positions
-// i + j s' share i's residue), so each rank runs the round on its own rows
-// with every size divided by W: its own table over its C / W commitments,
-// the look-ahead's folds and pairings over len / W positions, the h folds and
-// preparations of its positions, and the cross MSMs as partial sums over its
-// rows.  ONE all-gather per product combines them on every rank: the cross
-// partials summed (XYZZ), the Miller partials multiplied before the single
-// final exponentiation (gt_prod_final); every rank then combines t^(r) and
-// replays the transcript itself (no broadcast).  At the first round with
-// len < 4W the ranks gather the folded a^(r1) (len = 2W points) to rank 0,
-// which tabulates it and finishes the remaining rounds with the a-side
-// rebased on it (a^(r)_i = sum_{t < 2^(r - r1)} W_r[t] a^(r1)_{i + t len}:
-// the first weights of the same W_r) and the epilogue alone.  The exchange is
-// the caller's (tpst_exchange: RCCL, gloo, ...), ordered on a dedicated comm
-// stream so that every rank issues the same collectives in the same order.
-namespace {
-struct Shard {
-  int W = 1, rank = 0;
-  const tpst_exchange* x = nullptr;
-  const uint64_t* U = nullptr;  // c_u (canonical affine), every rank
-};
-
-size_t xch_align(size_t v) { return (v + 255) & ~(size_t)255; }
-size_t xch_slot(size_t bytes, int W) { return xch_align(bytes) + xch_align((size_t)W * bytes); }
-// first round whose look-ahead cannot be split over W ranks (len < 4W)
-int shard_rounds(int m, int W) {
-  int r1 = 0;
-  while (r1 < m && (((size_t)1 << m) >> r1) >= (size_t)4 * W) r1++;
-  return r1;
-}
-}  // namespace
-
-extern "C" size_t tpst_open_sharded_arena_bytes(int n, int world) {
-  if (n < 1 || n > 2 * TPST_MAX_VARS || world < 1 || (world & (world - 1))) return 0;
-  const int m = n / 2, r1 = shard_rounds(m, world);
-  if (r1 == 0) return 0;
-  constexpr size_t X1 = sizeof(Xyzz<Fq>), T12 = sizeof(Fq12);
-  return (size_t)r1 * (xch_slot(2 * X1, world) + xch_slot(8 * T12, world)) + xch_slot(2 * T12, world) +
-         xch_slot(2 * X1, world);
-}
-
-static int poly_open(tpst_ctx* ctx, tpst_poly* p, tpst_transcript* tr, int n, const uint64_t* comms,
-                     const uint64_t* point, tpst_open_proof* proof, const Shard* sh) {
-  const bool shd = sh != nullptr;
-  const int W = shd ? sh->W : 1, rho = shd ? sh->rank : 0;
-  const bool lead = rho == 0;  // produces the proof (and the PST proof of q)
-  std::lock_guard<tpst::CtxMutex> lk(ctx->mu);
-  if (lead)
-    if (int rc = poly_need_q_source(ctx, p)) return rc;
-  TPST_HIP(ctx, hipSetDevice(ctx->device));
-  SrsState* st = srs_of(ctx);
-  if (!st) return fail(ctx, TPST_E_STATE, "no SRS loaded");
-  int m, k, odd;
-  if (poly_dims(n, m, k, odd)) return fail(ctx, TPST_E_ARG, "bad num_vars");
-  if (st->nv != k) return fail(ctx, TPST_E_ARG, "SRS num_vars != ceil(n/2)");
-  for (size_t i = 0; i < ((size_t)2 << m); i++)
-    if (!fq_ok(comms + 6 * i)) return fail(ctx, TPST_E_ARG, "comm_list coordinate >= p");
-  if (lead && !p->has_q) {  // before the reference's open timer (sqrt_pst.rs:177-183)
-    int rc = poly_get_q(ctx, p, point);
-    if (rc) return rc;
-  }
-  TraceRange trace_open("sqrt_open");
-  Profiler& pf = ctx->prof;
-  pf.begin(ST_SQRT_OPEN, ctx->stream);
-  {
-    int rc = srs_fbt(ctx, st, odd);
-    if (rc) return rc;
-  }
-  const size_t C = (size_t)1 << m;
-  // the rounds split across the ranks: [0, r1); rank 0 alone from r1 on
-  const int r1 = shd ? shard_rounds(m, W) : 0;
-  const size_t Cl = C / W;  // a rank's rows (i = rho mod W)
-  std::unique_ptr<tpst_open_proof> own_proof;
-  if (!proof) {  // a rank other than 0 fills nothing the caller reads
-    own_proof.reset(new tpst_open_proof);
-    proof = own_proof.get();
-  }
-  memset(proof, 0, sizeof *proof);
-  proof->m_col = m;
-  proof->m_row = k;
-  Sponge sp;
-  sp.load(tr);
-
-  // ---- host staging layout (bytes): per-round uploads, final upload, downloads
-  std::vector<size_t> up_off(m + 2);
-  size_t off = 0;
-  // per round: c_{r-1}, c_{r-1}^-1, f_0..f_7 (Montgomery Fr), base-x digits of
-  // (c^-1, c, c^-1, c); the fold weights themselves are formed on the device
-  constexpr size_t UP_ROUND = 10 * 32 + 128;
-  for (int r = 0; r < m; r++) {
-    up_off[r] = off;
-    off += UP_ROUND;
-  }
-  up_off[m] = off;  // final: c_{m-1}, c_{m-1}^-1, rs (Montgomery Fr), a_rev (canonical Fr)
-  off += (2 + m + k) * 32;
-  const size_t up_bytes = off;
-  // downloads: U, each round's u_l / u_r as raw XYZZ (converted on the host)
-  // and t_l / t_r; final_a, final_h raw; pst_proof_h, pst_proof canonical
-  constexpr size_t X1 = sizeof(Xyzz<Fq>), X2 = sizeof(Xyzz<Fq2>), DN_ROUND = 2 * X1 + 1152;
-  const size_t dn_U = up_bytes, dn_round = dn_U + X1, dn_final = dn_round + (size_t)m * DN_ROUND;
-  const size_t dn_fh = dn_final + X1, dn_ph = dn_fh + X2, dn_pst = dn_ph + (size_t)m * 96;
-  const size_t dn_bytes = X1 + (size_t)m * DN_ROUND + X1 + X2 + (size_t)m * 96 + (size_t)k * 192;
-  const size_t n_ev = 9 + 6 * (size_t)m + (shd ? 8 * (size_t)m + 8 : 0);
-  // unsharded rebase: in round rb = 4, a^(4) (C / 16 points) is tabulated
-  // (as the sharded hand-over does) on the otherwise idle comm stream, and the
-  // later rounds fold 2^(r - 4) of its points instead of C / len row
-  // commitments (2^24 open 24.4 -> 23.0 ms, 2^20 10.4 -> 10.2 ms; rebasing at
-  // len 16 / 64 at 2^24 gained less: profiles/r06/ab/ab_open_rebase.txt)
-  const int rb = !shd && m >= 8 ? 4 : -1;
-  const size_t cm_off = up_bytes + dn_bytes;  // comm_list staging (unsharded form)
-  if (int rc = open_streams(ctx, n_ev, cm_off + (shd ? 0 : C * 96), shd || rb >= 0)) return rc;
-  uint8_t* pin = (uint8_t*)ctx->pinned;
-  // five streams: A (critical), B (cross terms), two look-ahead streams for
-  // alternating rounds (consecutive look-aheads overlap, each taking longer
-  // than a round) and C, the h preparation, at the greatest priority.  h^(r)
-  // (G2 fold + G2Prepared lines) is prepared in every round r >= 1 that a
-  // look-ahead needs: look-ahead r pairs E = 2^(r - s) fold sets of a^(r)
-  // against the prepared h^(s), s = r - 1 (prepared one round earlier: E = 2;
-  // in round 1 itself for r = 1: E = 1), s = 0 for r = 0.  Preparing at odd rounds only (s = r - 2 / r - 3, E =
-  // 4 / 8) paired two to four times as many pairs; C on stream A delayed the
-  // next round's t (2^24 open 26.6 -> 25.5 ms, 2^20 13.0 -> 11.4 ms with both,
-  // profiles/r05/i).  The epilogue's final h fold runs on the first look-ahead
-  // stream (idle by then), beside final_a (A) and pst_proof_h (B)
-  const hipStream_t sA = ctx->stream, sB = ctx->side[0], sC = ctx->side_c;
-  const hipStream_t sCe = ctx->side[1];
-  hipStream_t sLA[2] = {ctx->side[1], ctx->side[2]};
-  Arena &arA = ctx->arena, &arB = ctx->arena_side[0], &arC = ctx->arena2;
-  Arena* arLA[2] = {&ctx->arena_side[1], &ctx->arena_side[2]};
-  hipEvent_t* ev = ctx->events.data();
-  enum { EV_PRE, EV_TABLE, EV_U, EV_FINAL_UP, EV_B_DONE, EV_C_DONE, EV_D_DONE, EV_A_DONE, EV_REBASE };
-  auto ev_up = [&](int r) { return ev[9 + 6 * r]; };
-  auto ev_a = [&](int r) { return ev[9 + 6 * r + 1]; };
-  auto ev_b = [&](int r) { return ev[9 + 6 * r + 2]; };
-  auto ev_c = [&](int r) { return ev[9 + 6 * r + 3]; };
-  auto ev_la = [&](int r) { return ev[9 + 6 * r + 4]; };
-  auto ev_cl = [&](int r) { return ev[9 + 6 * r + 5]; };  // the rank's own h positions prepared
-  hipEvent_t* xev = ev + 9 + 6 * m;                         // exchange events (sharded form)
-  int last_c = -1;  // the last odd round that issued h work "C"
-  // the prepared h the look-ahead of round r pairs against (see above)
-  // look-ahead 1 pairs h^(1), prepared by C in round 1 (enqueued before D
-  // there), with E = 1 instead of h^(0) with E = 2: half the pairs (2^24 open
-  // 22.9 -> 22.5 ms, profiles/r06/ab/ab_open_la1.txt)
-  auto la_src = [](int r) { return r == 0 ? 0 : r - 1; };
-  // which odd rounds prepare h: for a look-ahead on the rank's own positions
-  // (local, sharded rounds) or on every position (global)
-  std::vector<char> need_loc(m + 1, 0), need_glob(m + 1, 0);
-  for (int r = 1; r < m; r++) {
-    if ((C >> r) < 4 || la_src(r) == 0) continue;
-    if (shd && r < r1)
-      need_loc[la_src(r)] = 1;
-    else if (lead)
-      need_glob[la_src(r)] = 1;
-  }
-
-  // ---- exchange (sharded form): slots in the caller's arena, one comm stream
-  size_t x_off = 0;
-  int x_n = 0;
-  struct Slot {
-    uint8_t* send;
-    uint8_t* recv;
-    size_t send_off, recv_off;
-  };
-  auto slot = [&](size_t bytes) {
-    Slot sl;
-    sl.send_off = x_off;
-    sl.recv_off = x_off + xch_align(bytes);
-    x_off += xch_slot(bytes, W);
-    sl.send = (uint8_t*)sh->x->d_arena + sl.send_off;
-    sl.recv = (uint8_t*)sh->x->d_arena + sl.recv_off;
-    return sl;
-  };
-  // every rank's `bytes` at its slot's send -> recv (rank-major), ordered
-  // after the work queued on `s` so far; `s` then waits for the result
-  auto gather = [&](hipStream_t s, const Slot& sl, size_t bytes) -> int {
-    hipEvent_t e0 = xev[2 * x_n], e1 = xev[2 * x_n + 1];
-    x_n++;
-    TPST_HIP(ctx, hipEventRecord(e0, s));
-    TPST_HIP(ctx, hipStreamWaitEvent(ctx->comm, e0, 0));
-    if (sh->x->allgather(sh->x->user, sl.send_off, sl.recv_off, bytes, (void*)ctx->comm))
-      return fail(ctx, TPST_E_STATE, "exchange all-gather failed");
-    TPST_HIP(ctx, hipEventRecord(e1, ctx->comm));
-    TPST_HIP(ctx, hipStreamWaitEvent(s, e1, 0));
-    return TPST_OK;
-  };
-  if (shd && (sh->x->arena_bytes < tpst_open_sharded_arena_bytes(n, W) || !sh->x->d_arena || !sh->x->allgather))
-    return fail(ctx, TPST_E_ARG, "exchange arena smaller than tpst_open_sharded_arena_bytes");
-
-  // ---- device buffers (allocated before any stream runs: no hipFree mid-open)
-  const size_t Ch = C > 1 ? C / 2 : 1;
-  const size_t Ca0 = shd ? Cl : C;  // a-side bases resident: own rows or all
-  auto& [up, A, P, Y, chiC, ScA, ScB, ScC, ScD, xa, xb, xd, xh, xp, xl, LAo, Hb, Lb, gts, canA, canC, canD, pstA, pstB,
-         Wall, Wiall, SqT, SqG, SqM, chis_own, tLoc, A1x, A1, tA1, Hbl, Lbl] = st->ob;
-  TPST_HIP(ctx, up.grow(up_bytes));
-  TPST_HIP(ctx, Wall.grow(2 * C * 32));  // round r's 2^r fold weights at offset 2^r - 1
-  TPST_HIP(ctx, Wiall.grow(2 * C * 32));
-  TPST_HIP(ctx, A.grow(Ca0 * 96));
-  TPST_HIP(ctx, P.grow(Ca0 * 96));
-  TPST_HIP(ctx, Y.grow(C * 32));
-  TPST_HIP(ctx, chiC.grow(C * 32));
-  TPST_HIP(ctx, ScA.grow(2 * C * 32));
-  TPST_HIP(ctx, ScB.grow(C * 32));
-  TPST_HIP(ctx, ScC.grow(C * 32));
-  TPST_HIP(ctx, xa.grow(C * sizeof(Xyzz<Fq>)));
-  TPST_HIP(ctx, xb.grow(2 * sizeof(Xyzz<Fq>)));
-  TPST_HIP(ctx, xd.grow((k + 1) * sizeof(Xyzz<Fq2>)));
-  TPST_HIP(ctx, xh.grow(C * sizeof(Xyzz<Fq2>)));
-  TPST_HIP(ctx, xp.grow(((size_t)m + 1) * sizeof(Xyzz<Fq>)));
-  for (int i = 0; i < 3; i++) {  // prepared h^(r) in slot r % 3
-    TPST_HIP(ctx, Hb[i].grow(Ch * 192));
-    TPST_HIP(ctx, Lb[i].grow(Ch * N_LINE_COEFFS * sizeof(LineCoeff)));
-    if (shd) {
-      TPST_HIP(ctx, Hbl[i].grow((Ch / W ? Ch / W : 1) * 192));
-      TPST_HIP(ctx, Lbl[i].grow((Ch / W ? Ch / W : 1) * N_LINE_COEFFS * sizeof(LineCoeff)));
-    }
-  }
-  TPST_HIP(ctx, gts.grow(2 * sizeof(Fq12)));
-  for (int i = 0; i < 2; i++) {
-    TPST_HIP(ctx, ScD[i].grow(8 * C * 32));
-    TPST_HIP(ctx, xl[i].grow(C * sizeof(Xyzz<Fq>)));
-    TPST_HIP(ctx, LAo[i].grow(8 * sizeof(Fq12)));
-    // sized for either engine (RNS form: rns::RES_WORDS u32 per Fq12)
-    TPST_HIP(ctx, SqT[i].grow(4 * 64 * MIPP_TAB_F12_BYTES));
-    TPST_HIP(ctx, SqG[i].grow(2 * 10 * MIPP_TAB_F12_BYTES));
-  }
-  TPST_HIP(ctx, SqM.grow(128 * MIPP_TAB_F12_BYTES));
-  TPST_HIP(ctx, canA.grow(2 * 576));
-  TPST_HIP(ctx, canC.grow((size_t)(m + 1) * 192));
-  TPST_HIP(ctx, canD.grow(96 + (size_t)k * 192));
-  TPST_HIP(ctx, pstA.grow(pst_open_scratch_words(st, m) * 4));
-  TPST_HIP(ctx, pstB.grow(pst_open_scratch_words(st, k) * 4));
-  if (!shd && st->t_A_n < C) {
-    TPST_HIP(ctx, st->t_A.alloc(fbt_words<Fq>(C) * 4));
-    st->t_A_n = C;
-  }
-  if (shd) TPST_HIP(ctx, tLoc.grow(fbt_words<Fq>(Cl) * 4));
-  if (shd || rb >= 0) {
-    const size_t len1 = C >> (shd ? r1 : rb);
-    TPST_HIP(ctx, A1x.grow(len1 * X1));
-    TPST_HIP(ctx, A1.grow(len1 * 96));
-    TPST_HIP(ctx, tA1.grow(fbt_words<Fq>(len1) * 4));
-  }
-  {  // G2 preparation scratch: the prepared h^(r) (global: <= C / 2 points, a rank's: <= C / 2W)
-    size_t mx = 0;
-    for (int r = 1; r <= m; r++) {
-      if (need_glob[r]) mx = std::max(mx, C >> r);
-      if (need_loc[r]) mx = std::max(mx, (C >> r) / W);
-    }
-    if (mx)
-      if (int rc = prep_scratch_for(ctx, st, mx)) return rc;
-  }
-  const uint32_t* H0 = st->ph[odd]->u();
-  const LineCoeff* L0 = (const LineCoeff*)st->hprep[odd].p;
-  const uint32_t* tH = st->t_h[odd].u();
-  // a rank's own positions of the SRS side (every W-th of h, its prepared
-  // lines and its table), cached per (W, rank, parity)
-  const uint32_t *H0l = H0, *tHl = tH;
-  const LineCoeff* L0l = L0;
-  if (shd) {
-    SrsState::Local& lc = st->local[odd];
-    if (lc.W != W || lc.rank != rho) {
-      const size_t tb = fbt_words<Fq2>(1) * 4;  // one point's table block
-      const size_t lb = sizeof(LineCoeff);
-      TPST_HIP(ctx, lc.H0.alloc(Cl * 192));
-      TPST_HIP(ctx, lc.L0.alloc(Cl * N_LINE_COEFFS * lb));
-      TPST_HIP(ctx, lc.tH.alloc(Cl * tb));
-      TPST_HIP(ctx, hipMemcpy2DAsync(lc.H0.p, 192, (const uint8_t*)H0 + 192 * rho, 192 * W, 192, Cl,
-                                     hipMemcpyDeviceToDevice, sA));
-      // coefficient-major [idx][pair]: row idx * Cl + j of the copy is column
-      // W (idx * Cl + j) + rho of the cache (C = W Cl)
-      TPST_HIP(ctx, hipMemcpy2DAsync(lc.L0.p, lb, (const uint8_t*)L0 + lb * rho, lb * W, lb, Cl * N_LINE_COEFFS,
-                                     hipMemcpyDeviceToDevice, sA));
-      TPST_HIP(ctx, hipMemcpy2DAsync(lc.tH.p, tb, (const uint8_t*)tH + tb * rho, tb * W, tb, Cl,
-                                     hipMemcpyDeviceToDevice, sA));
-      lc.W = W;
-      lc.rank = rho;
-    }
-    H0l = lc.H0.u();
-    L0l = (const LineCoeff*)lc.L0.p;
-    tHl = lc.tH.u();
-  }
-  const uint32_t* tA = shd ? tLoc.u() : st->t_A.u();  // the a-side table (rebased at the hand-over)
-  size_t Ca = Ca0;                                    // its base count
-  auto dup = [&](size_t byte_off) { return (uint32_t*)((uint8_t*)up.p + byte_off); };
-
-  // ---- prologue (stream A): this rank's comm_list rows -> Montgomery, y = chi(b), canonical chi
-  {
-    uint8_t* a_stage = pin + up_off[m] + (2 + m) * 32;  // a_rev (canonical) -> D
-    for (int i = 0; i < k; i++) memcpy(a_stage + 32 * i, point + 4 * (k - 1 - i), 32);
-  }
-  if (shd) {
-    std::vector<uint64_t> own(Cl * 12);
-    for (size_t j = 0; j < Cl; j++) memcpy(&own[12 * j], comms + 12 * (W * j + rho), 96);
-    TPST_HIP(ctx, hipMemcpyAsync(A.p, own.data(), Cl * 96, hipMemcpyHostToDevice, sA));
-    TPST_HIP(ctx, hipStreamSynchronize(sA));  // `own` is pageable and local
-  } else {
-    memcpy(pin + cm_off, comms, C * 96);  // pinned: an asynchronous copy, not HIP's pageable staging
-    TPST_HIP(ctx, hipMemcpyAsync(A.p, pin + cm_off, C * 96, hipMemcpyHostToDevice, sA));
-  }
-  TPST_HIP(ctx, points_to_mont<Fq>(sA, A.u(), A.u(), Ca0));
-  const uint32_t* chis = nullptr;
-  if (lead) {
-    chis = p->chis.u();
-  } else {
-    if (int rc = chi_b_table(ctx, m, k, point, chis_own)) return rc;
-    chis = chis_own.u();
-  }
-  TPST_HIP(ctx, hipMemcpyAsync(Y.p, chis, C * 32, hipMemcpyDeviceToDevice, sA));
-  TPST_HIP(ctx, fr_from_mont(sA, chis, chiC.u(), C));
-  TPST_HIP(ctx, hipEventRecord(ev[EV_PRE], sA));
-  for (hipStream_t s2 : {sB, sLA[0], sLA[1]}) TPST_HIP(ctx, hipStreamWaitEvent(s2, ev[EV_PRE], 0));
-  pf.begin(ST_MIPP_PROVE, sA);  // mipp.rs:38-149 (sqrt_pst.rs:211-214)
-  TraceRange trace_mipp("mipp_prove");
-
-  // ---- look-ahead stream 1 (idle until round 1): the fold table over comm_list
-  // (prebuilt by the commit of exactly these row commitments: used once), or
-  // over this rank's rows
-  if (shd) {
-    TPST_HIP(ctx, fbt_build<Fq>(*arLA[1], sLA[1], A.u(), Cl, tLoc.u(), true));
-  } else {
-    const bool prebuilt = st->t_A_key.size() == 12 * C && !memcmp(st->t_A_key.data(), comms, C * 96);
-    st->t_A_key.clear();
-    if (!prebuilt) TPST_HIP(ctx, fbt_build<Fq>(*arLA[1], sLA[1], A.u(), C, st->t_A.u(), true));
-  }
-  TPST_HIP(ctx, hipEventRecord(ev[EV_TABLE], sLA[1]));
-  // ---- stream B: U = MSM(comm_list, chi(b)) on that table, or the c_u the
-  // ranks combined
-  const uint64_t* U_given = shd ? sh->U : (p->has_u ? p->U : nullptr);
-  if (U_given) {
-    TPST_HIP(ctx, hipEventRecord(ev[EV_U], sB));
-  } else {
-    TPST_HIP(ctx, hipStreamWaitEvent(sB, ev[EV_TABLE], 0));
-    TraceRange trace_msm("msm");  // sqrt_pst.rs:188-199
-    pf.begin(ST_MSM_U, sB);
-    FbGroups gu;
-    gu.members = C;
-    gu.L = gu.D = C;
-    gu.glv = true;
-    TPST_HIP(ctx, fbt_msm<Fq>(arB, sB, tA, chiC.u(), gu, (Xyzz<Fq>*)xd.p));
-    pf.end(ST_MSM_U, sB);
-    TPST_HIP(ctx, hipMemcpyAsync(pin + dn_U, xd.p, X1, hipMemcpyDeviceToHost, sB));
-    TPST_HIP(ctx, hipEventRecord(ev[EV_U], sB));
-  }
-  // PST proof of q at a_rev (stream B, after round 0's cross terms)
-  auto pst_q = [&]() -> int {
-    TraceRange trace_pst("pst_open");  // sqrt_pst.rs:216-226
-    pf.begin(ST_PST_OPEN, sB);
-    const size_t a_off = up_off[m] + (2 + m) * 32;
-    TPST_HIP(ctx, hipMemcpyAsync(dup(a_off), pin + a_off, (size_t)k * 32, hipMemcpyHostToDevice, sB));
-    TPST_HIP(ctx, fr_to_mont(sB, dup(a_off), dup(a_off), k));
-    Xyzz<Fq2>* x2 = (Xyzz<Fq2>*)xd.p + 1;
-    TPST_HIP(ctx, pst_open_fbt_s<Fq2>(sB, arB, st, st->t_php.u(), st->nv - k, p->q.u(), k, dup(a_off), x2, pstB.u()));
-    TPST_HIP(ctx, xyzz_to_affine_canonical<Fq2>(sB, x2, canD.u() + 24, k));
-    TPST_HIP(ctx, hipMemcpyAsync(pin + dn_pst, canD.u() + 24, (size_t)k * 192, hipMemcpyDeviceToHost, sB));
-    pf.end(ST_PST_OPEN, sB);
-    return TPST_OK;
-  };
-  if (m == 0 && lead)
-    if (int rc = pst_q()) return rc;
-
-  // W_r[t] / Wi_r[t] (device, mipp_weights): products of the challenges
-  // (inverses) folded so far, so that a^(r)_i = sum_t W_r[t] a_{i + t len},
-  // h^(r)_i = sum_t Wi_r[t] h_{i + t len}
-  std::vector<Fr> xs_inv;
-  Fr cprev = Fr::one(), cprev_c = Fr::one();
-  uint64_t la_digits[16] = {};
-  bool have_U = false;
-  hipEvent_t ev_t1 = nullptr;  // the table over the gathered a^(r1) (rank 0, sharded form)
-  for (int r = 0; r < m; r++) {  // mipp.rs:58-120
-    const double hq = open_trace() ? host_us() : 0.0;
-    const size_t len = C >> r, s = len / 2, nW = (size_t)1 << r;
-    const bool loc = shd && r < r1;  // this round on the rank's own rows
-    // stage c_{r-1}, c_{r-1}^-1, the look-ahead factors and digits; upload
-    // once (stream B, whose previous work -- the round's comms_u -- is
-    // already done when the challenge exists: on A the upload queued behind
-    // A's wait for the look-ahead), form this round's weights there; A, C, D
-    // wait on it
-    uint8_t* stg = pin + up_off[r];
-    // look-ahead fold factors of h^(r) over h^(s), s = la_src(r): f_j = product
-    // of c'_{r-1-b} over the set bits b of j (offset j len of h^(s)'s row)
-    const int E = r == 0 ? 1 : 1 << (r - la_src(r));
-    Fr f[8];
-    f[0] = Fr::one();
-    for (int j = 1; j < E; j++) {
-      const int b = 31 - __builtin_clz((unsigned)j);
-      f[j] = mul(f[j ^ (1 << b)], xs_inv[r - 1 - b]);
-    }
-    memcpy(stg, cprev_c.v, 32);
-    memcpy(stg + 32, cprev.v, 32);
-    for (int j = 0; j < E; j++) memcpy(stg + 64 + 32 * j, f[j].v, 32);
-    memcpy(stg + 320, la_digits, 128);
-    uint32_t* dup_r = dup(up_off[r]);
-    uint32_t* dcp = dup_r + 8;   // c' = c_{r-1}^-1 (the y fold)
-    uint32_t* dfs = dup_r + 16;  // f_0..f_{E-1}
-    const uint64_t* ddig = (const uint64_t*)(dup_r + 80);
-    TPST_HIP(ctx, hipMemcpyAsync(dup_r, stg, UP_ROUND, hipMemcpyHostToDevice, sB));
-    TPST_HIP(ctx, mipp_weights(sB, Wall.u(), Wiall.u(), r, dup_r, dcp));
-    uint32_t* dW = Wall.u() + 8 * (nW - 1);
-    uint32_t* dWi = Wiall.u() + 8 * (nW - 1);
-    TPST_HIP(ctx, hipEventRecord(ev_up(r), sB));
-    // (round 0's A and D work -- the direct t and the first look-ahead --
-    // needs no upload: they do not wait behind B's U MSM)
-    if (r > 0) TPST_HIP(ctx, hipStreamWaitEvent(sA, ev_up(r), 0));
-
-    if (rb >= 0 && r == rb + 1) {  // the rebase table from here on (B waits for it; D, A do below)
-      tA = tA1.u();
-      Ca = C >> rb;
-      TPST_HIP(ctx, hipStreamWaitEvent(sB, ev_t1, 0));
-    }
-    if (shd && r == r1) {
-      // -- hand-over: a^(r1) (len = 2W positions) folded by the owners of its
-      // positions, gathered; rank 0 tabulates it and continues alone
-      const size_t per = len / W;
-      TPST_HIP(ctx, hipStreamWaitEvent(sB, ev[EV_TABLE], 0));
-      TPST_HIP(ctx, mipp_scalars(sB, dW, nullptr, len, 0, Cl, ScB.u(), W, rho));
-      FbGroups g;
-      g.groups = per;
-      g.members = C / len;
-      g.L = per;
-      g.D = 1;
-      g.glv = true;
-      const Slot sl = slot(per * X1);
-      TPST_HIP(ctx, fbt_msm<Fq>(arB, sB, tA, ScB.u(), g, (Xyzz<Fq>*)sl.send));
-      if (int rc = gather(sB, sl, per * X1)) return rc;
-      if (!lead) {  // this rank's part is done (its transcript stops here: tpst.h)
-        pf.end(ST_MIPP_PROVE, sA);
-        pf.end(ST_SQRT_OPEN, sA);
-        for (hipStream_t s2 : {sA, sB, sLA[0], sLA[1], sC, ctx->comm}) TPST_HIP(ctx, hipStreamSynchronize(s2));
-        sp.store(tr);
-        return TPST_OK;
-      }
-      // recv[w][j] = a^(r1) at position W j + w
-      for (int w = 0; w < W; w++)
-        TPST_HIP(ctx, hipMemcpy2DAsync((uint8_t*)A1x.p + w * X1, W * X1, sl.recv + (size_t)w * per * X1, X1, X1, per,
-                                       hipMemcpyDeviceToDevice, sB));
-      TPST_HIP(ctx, xyzz_to_affine_mont<Fq>(sB, (const Xyzz<Fq>*)A1x.p, A1.u(), len));
-      TPST_HIP(ctx, fbt_build<Fq>(arB, sB, A1.u(), len, tA1.u(), true));
-      ev_t1 = xev[2 * x_n];  // past the gathers' events
-      TPST_HIP(ctx, hipEventRecord(ev_t1, sB));
-      tA = tA1.u();
-      Ca = len;
-    }
-
-    uint8_t* dn_r = pin + dn_round + (size_t)r * DN_ROUND;
-    // -- A: t_l / t_r of this round, enqueued before B from round 1 on (the
-    // combination gates the odd rounds and needs only the upload, while B's
-    // table MSM costs the host tens of microseconds to enqueue; 2^20 open
-    // 11.40 -> 11.25 ms, 2^24 25.5 -> 24.9 ms, profiles/r06/ab/ab_open_order_prio.txt)
-    auto enqueue_a = [&]() -> int {
-      if (r == 0) {  // direct: the rotated comm_list (affine) against h^(0)
-        if (loc) {  // this rank's pairs (a_i, h_{s+i}), (a_{s+i}, h_i), i = rho mod W
-          TPST_HIP(ctx, affine_rot(sA, A.u(), P.u(), Cl, 24));
-          arA.reset();
-          TPST_HIP(ctx, arA.reserve(multi_pairing_scratch(2, s / W)));
-          const Slot sl = slot(2 * sizeof(Fq12));
-          TPST_HIP(ctx, multi_pairing_prepared(arA, sA, P.u(), H0l, L0l, 2, s / W, (Fq12*)sl.send, false, s / W, 0));
-          if (int rc = gather(sA, sl, 2 * sizeof(Fq12))) return rc;
-          TPST_HIP(ctx, gt_prod_final(sA, (const Fq12*)sl.recv, W, 2, (Fq12*)gts.p));
-        } else {
-          TPST_HIP(ctx, affine_rot(sA, A.u(), P.u(), C, 24));
-          arA.reset();
-          TPST_HIP(ctx, arA.reserve(multi_pairing_scratch(2, s)));
-          TPST_HIP(ctx, multi_pairing_prepared(arA, sA, P.u(), H0, L0, 2, s, (Fq12*)gts.p, true, s, 0));
-        }
-      } else {  // round r-1's look-ahead products, combined with c_{r-1}
-        TPST_HIP(ctx, hipStreamWaitEvent(sA, ev_la(r - 1), 0));
-        TPST_HIP(ctx, mipp_combine_tab(sA, (Fq12*)SqT[(r - 1) & 1].p, ddig, (Fq12*)SqG[(r - 1) & 1].p,
-                                       (Fq12*)SqM.p, (Fq12*)gts.p));
-      }
-      TPST_HIP(ctx, fq12_from_mont(sA, (Fq12*)gts.p, canA.u(), 2));
-      TPST_HIP(ctx, hipMemcpyAsync(dn_r + 2 * X1, canA.p, 1152, hipMemcpyDeviceToHost, sA));
-      TPST_HIP(ctx, hipEventRecord(ev_a(r), sA));
-      return TPST_OK;
-    };
-    const bool a_first = r > 0;
-    if (a_first)
-      if (int rc = enqueue_a()) return rc;
-    // -- B: y fold by the previous challenge, cross MSMs u_l / u_r
-    // (u_l = a[:s]^y[s:], u_r = a[s:]^y[:s], on the comm_list table); B goes
-    // before the look-ahead: its comms_u gate the transcript, and the
-    // look-ahead enqueue below costs the host tens of launches
-    TPST_HIP(ctx, hipStreamWaitEvent(sB, ev_up(r), 0));
-    if (r > 0) TPST_HIP(ctx, compress_fr(sB, Y.u(), len, dcp));  // y_l + c' y_r (mipp.rs:124-136)
-    {  // (round 0 as two variable-base K2 MSMs over comm_list, skipping the
-       // table build, measured slower: 3.4 vs 1.7 ms at 2^20)
-      TPST_HIP(ctx, hipStreamWaitEvent(sB, ev[EV_TABLE], 0));
-      FbGroups g;
-      g.groups = 2;
-      g.glv = true;
-      if (loc) {  // partial sums over this rank's rows, gathered and summed
-        TPST_HIP(ctx, mipp_scalars(sB, dW, Y.u(), len, s, Cl, ScB.u(), W, rho));
-        g.members = C / len * s / W;
-        g.L = len / W;
-        g.D = s / W;
-        const Slot sl = slot(2 * X1);
-        TPST_HIP(ctx, fbt_msm<Fq>(arB, sB, tA, ScB.u(), g, (Xyzz<Fq>*)sl.send));
-        if (int rc = gather(sB, sl, 2 * X1)) return rc;
-        TPST_HIP(ctx, xyzz_sum_groups(sB, (const Xyzz<Fq>*)sl.recv, W, 2, (Xyzz<Fq>*)xb.p));
-      } else {
-        TPST_HIP(ctx, mipp_scalars(sB, dW, Y.u(), len, s, Ca, ScB.u()));
-        g.members = Ca / len * s;
-        g.L = len;
-        g.D = s;
-        TPST_HIP(ctx, fbt_msm<Fq>(arB, sB, tA, ScB.u(), g, (Xyzz<Fq>*)xb.p));
-      }
-    }
-    TPST_HIP(ctx, hipMemcpyAsync(dn_r, xb.p, 2 * X1, hipMemcpyDeviceToHost, sB));
-    TPST_HIP(ctx, hipEventRecord(ev_b(r), sB));
-    const double hb = open_trace() ? host_us() : 0.0;
-    if (!a_first)
-      if (int rc = enqueue_a()) return rc;
-    const double ha = open_trace() ? host_us() : 0.0;
-    auto enqueue_c = [&]() -> int {
-      // -- C: h^(r) prepared for the look-ahead of round r+1: at this rank's
-      // positions (sharded look-aheads) and / or at all
-      const bool c_glob = need_glob[r];
-      if (need_loc[r] || c_glob) {
-        TPST_HIP(ctx, hipStreamWaitEvent(sC, ev_up(r), 0));
-        if (r >= 3) TPST_HIP(ctx, hipStreamWaitEvent(sC, ev_la(r - 2), 0));  // last reader of h^(r-3)'s slot
-      }
-      if (need_loc[r]) {
-        const size_t ln = len / W;
-        TPST_HIP(ctx, mipp_scalars(sC, dWi, nullptr, len, 0, Cl, ScC.u(), W, rho));
-        FbGroups g;
-        g.groups = ln;
-        g.members = C / len;
-        g.L = ln;
-        g.D = 1;
-        TPST_HIP(ctx, fbt_msm<Fq2>(arC, sC, tHl, ScC.u(), g, (Xyzz<Fq2>*)xh.p));
-        TPST_HIP(ctx, xyzz_to_affine_mont<Fq2>(sC, (Xyzz<Fq2>*)xh.p, Hbl[r % 3].u(), ln));
-        TPST_HIP(ctx, g2_prepare_batch(sC, Hbl[r % 3].u(), ln, (LineCoeff*)Lbl[r % 3].p,
-                                       st->prep_scratch.u()));
-        TPST_HIP(ctx, hipEventRecord(ev_cl(r), sC));
-        last_c = r;
-      }
-      if (c_glob) {
-        TPST_HIP(ctx, mipp_scalars(sC, dWi, nullptr, len, 0, C, ScC.u()));
-        FbGroups g;
-        g.groups = len;
-        g.members = C / len;
-        g.L = len;
-        g.D = 1;
-        TPST_HIP(ctx, fbt_msm<Fq2>(arC, sC, tH, ScC.u(), g, (Xyzz<Fq2>*)xh.p));
-        TPST_HIP(ctx, xyzz_to_affine_mont<Fq2>(sC, (Xyzz<Fq2>*)xh.p, Hb[r % 3].u(), len));
-        TPST_HIP(ctx, g2_prepare_batch(sC, Hb[r % 3].u(), len, (LineCoeff*)Lb[r % 3].p,
-                                       st->prep_scratch.u()));
-        TPST_HIP(ctx, hipEventRecord(ev_c(r), sC));
-        last_c = r;
-      }
-      return TPST_OK;
-    };
-    const bool c_first = r == 1;  // look-ahead 1 pairs this round's h
-    if (c_first)
-      if (int rc = enqueue_c()) return rc;
-    // -- D: look-ahead products of this round's vectors for round r+1
-    if (len >= 4) {
-      hipStream_t sD = sLA[r & 1];
-      Arena& arD = *arLA[r & 1];
-      if (r > 0) TPST_HIP(ctx, hipStreamWaitEvent(sD, ev_up(r), 0));
-      if (ev_t1) TPST_HIP(ctx, hipStreamWaitEvent(sD, ev_t1, 0));
-      const size_t ln = loc ? len / W : len;  // positions this rank pairs
-      arD.reset();
-      TPST_HIP(ctx, arD.reserve(mipp_lookahead_scratch(ln / 4, E) + 4096));
-      Slot sl{};
-      Fq12* la_out = (Fq12*)LAo[r & 1].p;
-      if (loc) {
-        sl = slot(8 * sizeof(Fq12));
-        la_out = (Fq12*)sl.send;
-      }
-      if (r == 0) {  // a^(0) = comm_list (affine), h^(0) prepared
-        if (loc)
-          TPST_HIP(ctx, mipp_lookahead(arD, sD, L0l, Cl, H0l, A.u(), false, ln, 1, la_out, false));
-        else
-          TPST_HIP(ctx, mipp_lookahead(arD, sD, L0, C, H0, A.u(), false, len, 1, la_out));
-      } else {
-        // E fold sets f_j a^(r): h^(r)_q = sum_j f_j h^(s)[q + j len]
-        TPST_HIP(ctx, hipStreamWaitEvent(sD, ev[EV_TABLE], 0));
-        uint32_t* sc = ScD[r & 1].u();
-        FbGroups g;
-        g.groups = ln;
-        g.L = ln;
-        g.D = 1;
-        g.sets = (size_t)E;
-        g.glv = true;
-        if (loc) {
-          TPST_HIP(ctx, mipp_scalar_sets(sD, dW, dfs, E, len, Cl, sc, W, rho));
-          g.members = C / len;
-          g.set_stride = Cl;
-        } else {
-          TPST_HIP(ctx, mipp_scalar_sets(sD, dW, dfs, E, len, Ca, sc));
-          g.members = Ca / len;
-          g.set_stride = Ca;
-        }
-        TPST_HIP(ctx, fbt_msm<Fq>(arD, sD, tA, sc, g, (Xyzz<Fq>*)xl[r & 1].p));
-        const int src = la_src(r);  // h^(0), or h^(src) prepared by stream C in round src
-        const uint32_t* hp = loc ? H0l : H0;
-        const LineCoeff* lp = loc ? L0l : L0;
-        if (src > 0) {
-          TPST_HIP(ctx, hipStreamWaitEvent(sD, loc ? ev_cl(src) : ev_c(src), 0));
-          hp = (loc ? Hbl : Hb)[src % 3].u();
-          lp = (const LineCoeff*)(loc ? Lbl : Lb)[src % 3].p;
-        }
-        TPST_HIP(ctx, mipp_lookahead(arD, sD, lp, (size_t)E * ln, hp, xl[r & 1].u(), true, ln, E, la_out, !loc));
-      }
-      if (loc) {
-        if (int rc = gather(sD, sl, 8 * sizeof(Fq12))) return rc;
-        TPST_HIP(ctx, gt_prod_final(sD, (const Fq12*)sl.recv, W, 8, (Fq12*)LAo[r & 1].p));
-      }
-      TPST_HIP(ctx, mipp_sq_tables(sD, (Fq12*)LAo[r & 1].p, (Fq12*)SqT[r & 1].p, (Fq12*)SqG[r & 1].p));
-      TPST_HIP(ctx, hipEventRecord(ev_la(r), sD));
-    }
-
-    const double hd = open_trace() ? host_us() : 0.0;
-    if (r == 0 && lead)
-      if (int rc = pst_q()) return rc;
-
-    const double hp = open_trace() ? host_us() : 0.0;
-    if (!c_first)
-      if (int rc = enqueue_c()) return rc;
-
-    if (r == rb) {  // the rebase (see rb above), consumed from round rb + 1 on
-      const hipStream_t sR = ctx->comm;
-      TPST_HIP(ctx, hipStreamWaitEvent(sR, ev_up(r), 0));
-      TPST_HIP(ctx, hipStreamWaitEvent(sR, ev[EV_TABLE], 0));
-      TPST_HIP(ctx, mipp_scalars(sR, dW, nullptr, len, 0, C, ScA.u()));
-      FbGroups g;
-      g.groups = len;
-      g.members = C / len;
-      g.L = len;
-      g.D = 1;
-      g.glv = true;
-      TPST_HIP(ctx, fbt_msm<Fq>(ctx->io, sR, tA, ScA.u(), g, (Xyzz<Fq>*)A1x.p));
-      TPST_HIP(ctx, xyzz_to_affine_mont<Fq>(sR, (const Xyzz<Fq>*)A1x.p, A1.u(), len));
-      TPST_HIP(ctx, fbt_build<Fq>(ctx->io, sR, A1.u(), len, tA1.u(), true));
-      ev_t1 = ev[EV_REBASE];
-      TPST_HIP(ctx, hipEventRecord(ev_t1, sR));
-    }
-
-    // -- host: transcript (mipp.rs:56, 97-101) and the challenge
-    if (!have_U) {
-      TPST_HIP(ctx, hipEventSynchronize(ev[EV_U]));
-      if (U_given)
-        memcpy(proof->U, U_given, 96);
-      else
-        xyzz_to_canonical_host<Fq>(pin + dn_U, 1, proof->U);
-      uint8_t b[96];
-      g1_bytes(proof->U, b);
-      sp.absorb_bytes(b, 96);
-      have_U = true;
-    }
-    // comms_u (stream B) is ready well before comms_t (the final
-    // exponentiations): absorb it while stream A finishes (mipp.rs:97-100
-    // order: u_l, u_r, t_l, t_r)
-    const double h0 = host_us();
-    TPST_HIP(ctx, hipEventSynchronize(ev_b(r)));
-    const double h1 = host_us();
-    xyzz_to_canonical_host<Fq>(dn_r, 2, proof->comms_u[r][0]);
-    uint8_t b[96];
-    g1_bytes(proof->comms_u[r][0], b);
-    sp.absorb_bytes(b, 96);
-    g1_bytes(proof->comms_u[r][1], b);
-    sp.absorb_bytes(b, 96);
-    const double h2 = host_us();
-    TPST_HIP(ctx, hipEventSynchronize(ev_a(r)));
-    const double h3 = host_us();
-    memcpy(proof->comms_t[r][0], dn_r + 2 * X1, 576);
-    memcpy(proof->comms_t[r][1], dn_r + 2 * X1 + 576, 576);
-    sp.absorb_bytes((const uint8_t*)proof->comms_t[r][0], 576);
-    sp.absorb_bytes((const uint8_t*)proof->comms_t[r][1], 576);
-    const double h4 = host_us();
-    uint64_t ci_c[4];
-    sp.challenge(ci_c);  // mipp.rs:101
-    const Fr c_inv = fr_canon(ci_c);
-    const double h5 = host_us();
-    const Fr c = fr_inv(c_inv);  // mipp.rs:106
-    if (open_trace())
-      fprintf(stderr,
-              "open round %d%s: enqueue %.0f (B %.0f A %.0f D %.0f pst %.0f C %.0f) wait_u %.0f absorb_u %.0f wait_t %.0f "
-              "absorb_t %.0f challenge %.0f inv %.0f us\n",
-              r, loc ? " (sharded)" : "", h0 - hq, hb - hq, ha - hb, hd - ha, hp - hd, h0 - hp, h1 - h0, h2 - h1,
-              h3 - h2, h4 - h3, h5 - h4, host_us() - h5);
-    xs_inv.push_back(c_inv);
-    cprev = c_inv;
-    cprev_c = c;
-    // base-x digits of (c^-1, c, c^-1, c) for the next round's combination
-    {
-      uint64_t ci[4], cc[4];
-      fr_out(c_inv, ci);
-      fr_out(c, cc);
-      base_x_digits(ci, la_digits);
-      base_x_digits(cc, la_digits + 4);
-      memcpy(la_digits + 8, la_digits, 64);
-    }
-  }
-  if (!have_U) {
-    TPST_HIP(ctx, hipEventSynchronize(ev[EV_U]));
-    if (U_given)
-      memcpy(proof->U, U_given, 96);
-    else
-      xyzz_to_canonical_host<Fq>(pin + dn_U, 1, proof->U);
-    uint8_t b[96];
-    g1_bytes(proof->U, b);
-    sp.absorb_bytes(b, 96);
-  }
-
-  // ---- epilogue: final_a (A), final_h (C), pst_proof_h (B); rs need only the
-  // transcript state after the last round (mipp.rs:138-141)
-  // final weights W_m, Wi_m (device); the p_h evaluations of mipp.rs:159-180,
-  // prod over the set bits j of t of c^-1_{m-1-j}, are exactly Wi_m[t]
-  {
-    uint8_t* stg = pin + up_off[m];
-    memcpy(stg, cprev_c.v, 32);
-    memcpy(stg + 32, cprev.v, 32);
-    for (int i = 0; i < m; i++) {
-      uint64_t cc[4];
-      sp.challenge(cc);
-      const Fr rr = fr_canon(cc);
-      memcpy(stg + 32 * (2 + i), rr.v, 32);
-    }
-  }
-  uint32_t* dfin = dup(up_off[m]);
-  TPST_HIP(ctx, hipMemcpyAsync(dfin, pin + up_off[m], (2 + m) * 32, hipMemcpyHostToDevice, sA));
-  TPST_HIP(ctx, mipp_weights(sA, Wall.u(), Wiall.u(), m, dfin, dfin + 8));
-  const uint32_t* dWm = Wall.u() + 8 * (C - 1);
-  const uint32_t* dWim = Wiall.u() + 8 * (C - 1);
-  TPST_HIP(ctx, hipEventRecord(ev[EV_FINAL_UP], sA));
-  TPST_HIP(ctx, hipStreamWaitEvent(sA, ev[EV_TABLE], 0));
-  if (ev_t1) TPST_HIP(ctx, hipStreamWaitEvent(sA, ev_t1, 0));
-  {  // final_a = a^(m)_0 (one group over the a-side bases: all C, or the gathered a^(r1))
-    FbGroups g;
-    g.members = Ca;
-    TPST_HIP(ctx, mipp_scalars(sA, dWm, nullptr, 1, 0, Ca, ScA.u()));
-    g.glv = true;
-    TPST_HIP(ctx, fbt_msm<Fq>(arA, sA, tA, ScA.u(), g, (Xyzz<Fq>*)xa.p));
-    TPST_HIP(ctx, hipMemcpyAsync(pin + dn_final, xa.p, X1, hipMemcpyDeviceToHost, sA));
-  }
-  TPST_HIP(ctx, hipStreamWaitEvent(sCe, ev[EV_FINAL_UP], 0));
-  if (last_c >= 0) TPST_HIP(ctx, hipStreamWaitEvent(sCe, ev_c(last_c), 0));  // xh / ScC / arC reuse
-  if (last_c >= 0 && need_loc[last_c]) TPST_HIP(ctx, hipStreamWaitEvent(sCe, ev_cl(last_c), 0));
-  {  // final_h = h^(m)_0
-    FbGroups g;
-    g.members = C;
-    TPST_HIP(ctx, mipp_scalars(sCe, dWim, nullptr, 1, 0, C, ScC.u()));
-    TPST_HIP(ctx, fbt_msm<Fq2>(arC, sCe, tH, ScC.u(), g, (Xyzz<Fq2>*)xh.p));
-    TPST_HIP(ctx, hipMemcpyAsync(pin + dn_fh, xh.p, X2, hipMemcpyDeviceToHost, sCe));
-    TPST_HIP(ctx, hipEventRecord(ev[EV_C_DONE], sCe));
-  }
-  if (m > 0) {  // pst_proof_h = open_g1(p_h, rs) (mipp.rs:144)
-    TPST_HIP(ctx, hipStreamWaitEvent(sB, ev[EV_FINAL_UP], 0));
-    TPST_HIP(ctx, pst_open_fbt_s<Fq>(sB, arB, st, st->t_pgp.u(), st->nv - m, dWim, m, dfin + 16,
-                                     (Xyzz<Fq>*)xp.p, pstA.u()));
-    TPST_HIP(ctx, xyzz_to_affine_canonical<Fq>(sB, (Xyzz<Fq>*)xp.p, canC.u() + 48, m));
-    TPST_HIP(ctx, hipMemcpyAsync(pin + dn_ph, canC.u() + 48, (size_t)m * 96, hipMemcpyDeviceToHost, sB));
-  }
-  TPST_HIP(ctx, hipEventRecord(ev[EV_B_DONE], sB));
-  if (pf.on) {  // device spans end when every stream of the opening has drained
-    TPST_HIP(ctx, hipEventRecord(ev[EV_D_DONE], sLA[0]));
-    TPST_HIP(ctx, hipEventRecord(ev[EV_A_DONE], sLA[1]));
-    for (int e : {(int)EV_B_DONE, (int)EV_C_DONE, (int)EV_D_DONE, (int)EV_A_DONE})
-      TPST_HIP(ctx, hipStreamWaitEvent(sA, ev[e], 0));
-    pf.end(ST_MIPP_PROVE, sA);
-    pf.end(ST_SQRT_OPEN, sA);
-  }
-  for (hipStream_t s2 : {sA, sB, sLA[0], sLA[1], sC}) TPST_HIP(ctx, hipStreamSynchronize(s2));
-  if (shd || rb >= 0) TPST_HIP(ctx, hipStreamSynchronize(ctx->comm));
-  xyzz_to_canonical_host<Fq>(pin + dn_final, 1, proof->final_a);
-  xyzz_to_canonical_host<Fq2>(pin + dn_fh, 1, proof->final_h);
-  if (m > 0) memcpy(proof->pst_proof_h, pin + dn_ph, (size_t)m * 96);
-  memcpy(proof->pst_proof, pin + dn_pst, (size_t)k * 192);
-  sp.store(tr);
-  return TPST_OK;
-}
-
-extern "C" int tpst_poly_open(tpst_ctx* ctx, tpst_poly* p, tpst_transcript* tr, const uint64_t* comms,
-                              const uint64_t* point, const uint64_t* T, tpst_open_proof* proof) {
-  (void)T;  // the reference passes T but the prover does not use it (mipp.rs:38)
-  if (!ctx || !p || !tr || !comms || !point || !proof) return fail(ctx, TPST_E_ARG, "null argument");
-  return poly_open(ctx, p, tr, p->n, comms, point, proof, nullptr);
-}
-
-extern "C" int tpst_poly_open_sharded(tpst_ctx* ctx, tpst_poly* p, tpst_transcript* tr, int n, const uint64_t* comms,
-                                      const uint64_t* point, const uint64_t* U, const tpst_exchange* x,
-                                      tpst_open_proof* proof) {
-  if (!ctx || !tr || !comms || !point || !U || !x) return fail(ctx, TPST_E_ARG, "null argument");
-  if (x->world < 1 || (x->world & (x->world - 1)) || x->rank < 0 || x->rank >= x->world)
-    return fail(ctx, TPST_E_ARG, "world must be a power of two and 0 <= rank < world");
-  if (x->rank == 0 && (!p || !proof)) return fail(ctx, TPST_E_ARG, "rank 0 needs the opening handle and the proof");
-  if (p && p->n != n) return fail(ctx, TPST_E_ARG, "handle num_vars != n");
-  if (!point_valid<Fq>(U)) return fail(ctx, TPST_E_ARG, "c_u is not a valid G1 point");
-  for (int i = 0; i < n; i++)
-    if (!fr_ok(point + 4 * i)) return fail(ctx, TPST_E_ARG, "point coordinate >= r");
-  const int m = n / 2;
-  if (shard_rounds(m, x->world) == 0) {  // too few rows to split: rank 0 opens alone
-    if (x->rank != 0) return TPST_OK;
-    const bool had = p->has_u;
-    uint64_t keep[12];
-    memcpy(keep, p->U, 96);
-    memcpy(p->U, U, 96);
-    p->has_u = true;
-    const int rc = poly_open(ctx, p, tr, n, comms, point, proof, nullptr);
-    memcpy(p->U, keep, 96);
-    p->has_u = had;
-    return rc;
-  }
-  Shard sh;
-  sh.W = x->world;
-  sh.rank = x->rank;
-  sh.x = x;
-  sh.U = U;
-  return poly_open(ctx, p, tr, n, comms, point, proof, &sh);
 }
 
 // -------------------------------------------------------------- verify ---

@@ -29,8 +29,6 @@
 
 using namespace tpst;
 
-const uint32_t* tpst_internal_poly_evals(const tpst_poly* p);  // pst_api.hip
-
 #define TPST_TRY_HIP(x)                \
   do {                                 \
     hipError_t _e = (x);               \
@@ -444,11 +442,11 @@ Fr uni_eval(const Fr* cs, int n, const Fr& r) {
 
 // CSR (by key = rows) or CSC (by key = cols) of one matrix from device triples
 static hipError_t build_compressed(hipStream_t s, const uint32_t* key, const uint32_t* other, const uint32_t* val,
-                                   size_t nnz, size_t nkeys, Buf& ptr, Buf& idx, Buf& vout) {
+                                   size_t nnz, size_t nkeys, DevBuf& ptr, DevBuf& idx, DevBuf& vout) {
   TPST_TRY_HIP(ptr.alloc((nkeys + 1) * 4));
   TPST_TRY_HIP(idx.alloc(nnz ? nnz * 4 : 4));
   TPST_TRY_HIP(vout.alloc(nnz ? nnz * 32 : 32));
-  Buf cnt, cursor, tmp;
+  DevBuf cnt, cursor, tmp;
   TPST_TRY_HIP(cnt.alloc((nkeys + 1) * 4));
   TPST_TRY_HIP(cursor.alloc((nkeys + 1) * 4));
   TPST_TRY_HIP(hipMemsetAsync(cnt.p, 0, (nkeys + 1) * 4, s));
@@ -503,14 +501,14 @@ extern "C" int tpst_r1cs_load(tpst_ctx* ctx, size_t num_cons, size_t num_vars, s
   R->num_vars = num_vars;
   R->num_inputs = num_inputs;
   R->ncols = 2 * num_vars;
-  Buf dr[3], dc[3], dv[3];
+  DevBuf dr[3], dc[3], dv[3];
   const uint32_t *pr[3], *pc[3], *pv[3];
   for (int m = 0; m < 3; m++) {
     R->nnz[m] = nnz[m];
     if (nnz[m] && (!rows[m] || !cols[m] || !vals[m])) return fail(ctx, TPST_E_ARG, "null matrix");
     for (size_t e = 0; e < nnz[m]; e++) {
       if (rows[m][e] >= num_cons || cols[m][e] >= R->ncols) return fail(ctx, TPST_E_ARG, "entry out of range");
-      if (!fr_ok_host(vals[m] + 4 * e)) return fail(ctx, TPST_E_ARG, "matrix value >= r");
+      if (!fr_ok(vals[m] + 4 * e)) return fail(ctx, TPST_E_ARG, "matrix value >= r");
     }
     TPST_HIP(ctx, dr[m].alloc(nnz[m] * 4 + 4));
     TPST_HIP(ctx, dc[m].alloc(nnz[m] * 4 + 4));
@@ -548,7 +546,7 @@ extern "C" int tpst_r1cs_synthetic(tpst_ctx* ctx, size_t num_cons, size_t num_va
   R->num_vars = num_vars;
   R->num_inputs = num_inputs;
   R->ncols = 2 * num_vars;
-  Buf dZ, rows, cols, vals;
+  DevBuf dZ, rows, cols, vals;
   TPST_HIP(ctx, dZ.alloc(sz * 32));
   TPST_HIP(ctx, rows.alloc(3 * num_cons * 4));
   TPST_HIP(ctx, cols.alloc(3 * num_cons * 4));
@@ -574,11 +572,11 @@ extern "C" int tpst_unipoly_from_evals(const uint64_t* evals, int n, uint64_t* c
   if (!evals || !coeffs || (n != 3 && n != 4)) return TPST_E_ARG;
   Fr e[4], cs[4];
   for (int i = 0; i < n; i++) {
-    if (!fr_ok_host(evals + 4 * i)) return TPST_E_ARG;
-    e[i] = frc(evals + 4 * i);
+    if (!fr_ok(evals + 4 * i)) return TPST_E_ARG;
+    e[i] = fr_canon(evals + 4 * i);
   }
   from_evals(e, n, cs);
-  for (int i = 0; i < n; i++) fro(cs[i], coeffs + 4 * i);
+  for (int i = 0; i < n; i++) fr_out(cs[i], coeffs + 4 * i);
   return TPST_OK;
 }
 
@@ -588,14 +586,14 @@ extern "C" int tpst_eq_evals(tpst_ctx* ctx, const uint64_t* r, int ell, uint64_t
   if (!ctx || !r || !out || ell < 0 || ell > 30) return fail(ctx, TPST_E_ARG, "eq_evals: bad argument");
   std::vector<Fr> rm(ell ? ell : 1);
   for (int j = 0; j < ell; j++) {
-    if (!fr_ok_host(r + 4 * j)) return fail(ctx, TPST_E_ARG, "eq_evals: r_j >= r");
-    rm[j] = frc(r + 4 * j);
+    if (!fr_ok(r + 4 * j)) return fail(ctx, TPST_E_ARG, "eq_evals: r_j >= r");
+    rm[j] = fr_canon(r + 4 * j);
   }
   const size_t n = (size_t)1 << ell;
   std::lock_guard<tpst::CtxMutex> lk(ctx->mu);
   TPST_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  Buf dr, dt;
+  DevBuf dr, dt;
   TPST_HIP(ctx, dr.alloc(rm.size() * 32));
   TPST_HIP(ctx, dt.alloc(n * 32));
   TPST_HIP(ctx, hipMemcpyAsync(dr.p, rm.data(), rm.size() * 32, hipMemcpyHostToDevice, s));
@@ -604,7 +602,7 @@ extern "C" int tpst_eq_evals(tpst_ctx* ctx, const uint64_t* r, int ell, uint64_t
   std::vector<Fr> h(n);
   TPST_HIP(ctx, hipMemcpyAsync(h.data(), dt.p, n * 32, hipMemcpyDeviceToHost, s));
   TPST_HIP(ctx, hipStreamSynchronize(s));
-  for (size_t i = 0; i < n; i++) fro(h[i], out + 4 * i);
+  for (size_t i = 0; i < n; i++) fr_out(h[i], out + 4 * i);
   return TPST_OK;
 }
 
@@ -616,7 +614,7 @@ static int sumcheck(tpst_ctx* ctx, void* pin, uint32_t* const* tabs, int rounds,
   hipStream_t s = ctx->stream;
   const size_t n0 = (size_t)1 << rounds;
   const size_t nblk0 = grid_for(n0 / 2, SC_BS);
-  Buf partial, sums, dr;
+  DevBuf partial, sums, dr;
   TPST_HIP(ctx, partial.alloc(nblk0 * 3 * 32));
   TPST_HIP(ctx, sums.alloc(3 * 32));
   TPST_HIP(ctx, dr.alloc(32));
@@ -639,18 +637,18 @@ static int sumcheck(tpst_ctx* ctx, void* pin, uint32_t* const* tabs, int rounds,
     TPST_HIP(ctx, hipMemcpyAsync(hs, sums.p, 96, hipMemcpyDeviceToHost, s));
     TPST_HIP(ctx, hipStreamSynchronize(s));
     // evals at 0, 1 (= e - eval(0)), 2, 3 (sumcheck.rs:127-128, 427)
-    Fr ev[4] = {frc(hs[0]), Fr::zero(), frc(hs[1]), frc(hs[2])};
+    Fr ev[4] = {fr_canon(hs[0]), Fr::zero(), fr_canon(hs[1]), fr_canon(hs[2])};
     ev[1] = sub(e, ev[0]);
     Fr cs[4];
     from_evals(ev, NC, cs);
     for (int c = 0; c < NC; c++) {
       uint64_t* out = polys + 4 * ((size_t)j * NC + c);
-      fro(cs[c], out);
+      fr_out(cs[c], out);
       if (tpst_transcript_append_fr(tr, out) != TPST_OK) return fail(ctx, TPST_E_ARG, "transcript append");
     }
     uint64_t rc[4];
     tpst_transcript_challenge(tr, rc);
-    rs[j] = frc(rc);
+    rs[j] = fr_canon(rc);
     e = uni_eval(cs, NC, rs[j]);
     memcpy(rpin, rs[j].v, 32);
     TPST_HIP(ctx, hipMemcpyAsync(dr.p, rpin, 32, hipMemcpyHostToDevice, s));
@@ -663,7 +661,7 @@ static int sumcheck(tpst_ctx* ctx, void* pin, uint32_t* const* tabs, int rounds,
   return TPST_OK;
 }
 
-static void fr_copy_out(const Fr& a, uint64_t* o) { fro(a, o); }
+static void fr_copy_out(const Fr& a, uint64_t* o) { fr_out(a, o); }
 
 // R1CSProof::prove (r1csproof.rs:237-370) without prove_verifier: the
 // polynomial commitment of the witness (sqrt-PST commit, its GT appended),
@@ -678,9 +676,9 @@ extern "C" int tpst_r1cs_prove(tpst_ctx* ctx, tpst_r1cs* R, const uint64_t* vars
   if (rx_n > TPST_R1CS_MAX_ROUNDS || ry_n > TPST_R1CS_MAX_ROUNDS || nvar_bits > 2 * TPST_MAX_VARS)
     return fail(ctx, TPST_E_ARG, "instance too large for tpst_r1cs_proof");
   for (size_t i = 0; i < R->num_vars; i++)
-    if (!fr_ok_host(vars + 4 * i)) return fail(ctx, TPST_E_ARG, "witness value >= r");
+    if (!fr_ok(vars + 4 * i)) return fail(ctx, TPST_E_ARG, "witness value >= r");
   for (size_t i = 0; i < R->num_inputs; i++)
-    if (!fr_ok_host(inputs + 4 * i)) return fail(ctx, TPST_E_ARG, "input value >= r");
+    if (!fr_ok(inputs + 4 * i)) return fail(ctx, TPST_E_ARG, "input value >= r");
   out->rounds_x = rx_n;
   out->rounds_y = ry_n;
   out->num_vars_log = nvar_bits;
@@ -699,7 +697,7 @@ extern "C" int tpst_r1cs_prove(tpst_ctx* ctx, tpst_r1cs* R, const uint64_t* vars
   for (int j = 0; j < rx_n; j++) {
     uint64_t c[4];
     tpst_transcript_challenge(tr, c);
-    tau[j] = frc(c);
+    tau[j] = fr_canon(c);
   }
   Fr fin1[4], fin2[2];
   Fr rA, rB, rC;
@@ -708,8 +706,8 @@ extern "C" int tpst_r1cs_prove(tpst_ctx* ctx, tpst_r1cs* R, const uint64_t* vars
     TPST_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const size_t M = R->num_cons, Nz = R->ncols;
-    Buf dins, z, tabs[4], dtau, drx, coef, abc;
-    const uint32_t* d_vars = tpst_internal_poly_evals(pl);  // uploaded once, by from_evaluations
+    DevBuf dins, z, tabs[4], dtau, drx, coef, abc;
+    const uint32_t* d_vars = poly_evals(pl);  // uploaded once, by from_evaluations
     if (!d_vars) return fail(ctx, TPST_E_STATE, "witness polynomial not resident");
     TPST_HIP(ctx, dins.alloc(R->num_inputs * 32 + 32));
     TPST_HIP(ctx, z.alloc(Nz * 32));
@@ -736,11 +734,11 @@ extern "C" int tpst_r1cs_prove(tpst_ctx* ctx, tpst_r1cs* R, const uint64_t* vars
     fr_copy_out(mul(az, bz), out->claims_phase2[3]);
     uint64_t c[4];
     tpst_transcript_challenge(tr, c);
-    rA = frc(c);
+    rA = fr_canon(c);
     tpst_transcript_challenge(tr, c);
-    rB = frc(c);
+    rB = fr_canon(c);
     tpst_transcript_challenge(tr, c);
-    rC = frc(c);
+    rC = fr_canon(c);
     const Fr claim2 = add(add(mul(rA, az), mul(rB, bz)), mul(rC, cz));
     // evals_ABC (r1csproof.rs:326-338) into tabs[1]; eq(rx, .) into tabs[0]
     TPST_HIP(ctx, drx.alloc(rx_n * 32));
@@ -764,11 +762,11 @@ extern "C" int tpst_r1cs_prove(tpst_ctx* ctx, tpst_r1cs* R, const uint64_t* vars
     fr_copy_out(fin2[0], out->claims_phase2_z_abc[0]);
     fr_copy_out(fin2[1], out->claims_phase2_z_abc[1]);
   }
-  for (int j = 0; j < rx_n; j++) fro(rx[j], out->rx[j]);
-  for (int j = 0; j < ry_n; j++) fro(ry[j], out->ry[j]);
-  fro(rA, out->r_abc[0]);
-  fro(rB, out->r_abc[1]);
-  fro(rC, out->r_abc[2]);
+  for (int j = 0; j < rx_n; j++) fr_out(rx[j], out->rx[j]);
+  for (int j = 0; j < ry_n; j++) fr_out(ry[j], out->ry[j]);
+  fr_out(rA, out->r_abc[0]);
+  fr_out(rB, out->r_abc[1]);
+  fr_out(rC, out->r_abc[2]);
   tpst_transcript_challenge(tr, out->transcript_sat_state);
   tpst_transcript_reset_fr(tr, out->transcript_sat_state);
   // ---- PST opening of the witness at ry[1..] (r1csproof.rs:349-357)
@@ -803,7 +801,7 @@ extern "C" int tpst_r1cs_commit(tpst_ctx* ctx, tpst_r1cs* R, const uint8_t* labe
   *mem_rows = L_mem;
   if (!comm_ops || !comm_mem) return TPST_OK;  // size query
   if (3 * N >= ((size_t)1 << 31)) return fail(ctx, TPST_E_ARG, "instance too large");
-  Buf ops, mem;
+  DevBuf ops, mem;
   {
     std::lock_guard<tpst::CtxMutex> lk(ctx->mu);
     TPST_HIP(ctx, hipSetDevice(ctx->device));
@@ -812,7 +810,7 @@ extern "C" int tpst_r1cs_commit(tpst_ctx* ctx, tpst_r1cs* R, const uint8_t* labe
     TPST_HIP(ctx, ops.alloc(16 * N * 32));
     TPST_HIP(ctx, mem.alloc(2 * cells * 32));
     TPST_HIP(ctx, hipMemsetAsync(ops.p, 0, 16 * N * 32, s));
-    Buf addr, pos, skey, spos, rts, audit, tmp;
+    DevBuf addr, pos, skey, spos, rts, audit, tmp;
     TPST_HIP(ctx, addr.alloc(M3 * 4));
     TPST_HIP(ctx, pos.alloc(M3 * 4));
     TPST_HIP(ctx, skey.alloc(M3 * 4));
@@ -821,7 +819,7 @@ extern "C" int tpst_r1cs_commit(tpst_ctx* ctx, tpst_r1cs* R, const uint8_t* labe
     TPST_HIP(ctx, audit.alloc(cells * 4));
     TPST_HIP(ctx, tmp.alloc(scan_sort::sort_scratch(M3) * 4));
     for (int rc = 0; rc < 2; rc++) {  // rows, then columns
-      const Buf* o = rc ? R->ocol : R->orow;
+      const DevBuf* o = rc ? R->ocol : R->orow;
       k_ops_addr<<<grid_for(M3, 256), 256, 0, s>>>(o[0].u(), o[1].u(), o[2].u(), (uint32_t)R->nnz[0],
                                                    (uint32_t)R->nnz[1], (uint32_t)R->nnz[2], N, addr.u(), pos.u());
       TPST_HIP(ctx, hipGetLastError());
@@ -846,7 +844,7 @@ extern "C" int tpst_r1cs_commit(tpst_ctx* ctx, tpst_r1cs* R, const uint8_t* labe
   }
   // the two Hyrax commitments (the library calls below take the context lock)
   struct Job {
-    const Buf* buf;
+    const DevBuf* buf;
     size_t L, Rn;
     uint64_t* out;
   } jobs[2] = {{&ops, L_ops, R_ops, comm_ops}, {&mem, L_mem, R_mem, comm_mem}};
@@ -856,7 +854,7 @@ extern "C" int tpst_r1cs_commit(tpst_ctx* ctx, tpst_r1cs* R, const uint8_t* labe
     tpst_gens* gens = nullptr;
     if (int rc = tpst_gens_load(ctx, G.data(), j.Rn, h.data(), &gens)) return rc;
     std::unique_ptr<tpst_gens, void (*)(tpst_gens*)> gg(gens, tpst_gens_free);
-    Buf dout;
+    DevBuf dout;
     TPST_HIP(ctx, dout.alloc(j.L * 96));
     if (int rc = tpst_g1_msm_batch_dev(ctx, gens, j.buf->p, j.L, j.Rn, j.Rn, 1, dout.p)) return rc;
     TPST_HIP(ctx, hipMemcpyAsync(j.out, dout.p, j.L * 96, hipMemcpyDeviceToHost, ctx->stream));
@@ -866,8 +864,6 @@ extern "C" int tpst_r1cs_commit(tpst_ctx* ctx, tpst_r1cs* R, const uint8_t* labe
 }
 
 // ================================================== evaluate / verify ====
-int tpst_internal_srs_nv(tpst_ctx* ctx);  // pst_api.hip
-
 // R1CSInstance::evaluate (r1csinstance.rs:308-311): both eq tables and the
 // gather-multiply-reduce on the device; every buffer is allocated before the
 // first launch.
@@ -879,8 +875,8 @@ extern "C" int tpst_r1cs_evaluate(tpst_ctx* ctx, tpst_r1cs* R, const uint64_t* r
   std::vector<Fr> pt((size_t)rx_n + ry_n);
   for (int j = 0; j < rx_n + ry_n; j++) {
     const uint64_t* c = j < rx_n ? rx + 4 * j : ry + 4 * (j - rx_n);
-    if (!fr_ok_host(c)) return fail(ctx, TPST_E_ARG, "evaluate: coordinate >= r");
-    pt[j] = frc(c);
+    if (!fr_ok(c)) return fail(ctx, TPST_E_ARG, "evaluate: coordinate >= r");
+    pt[j] = fr_canon(c);
   }
   std::lock_guard<tpst::CtxMutex> lk(ctx->mu);
   TPST_HIP(ctx, hipSetDevice(ctx->device));
@@ -890,7 +886,7 @@ extern "C" int tpst_r1cs_evaluate(tpst_ctx* ctx, tpst_r1cs* R, const uint64_t* r
   const unsigned nblk = full < EV_MAX_BLOCKS ? full : EV_MAX_BLOCKS;
   // each eq table is the outer product of the tables of its point's halves
   const int xl = rx_n / 2, xh = rx_n - xl, yl = ry_n / 2, yh = ry_n - yl;
-  Buf dpt, ex, ey, half[4], partial, dout;
+  DevBuf dpt, ex, ey, half[4], partial, dout;
   TPST_HIP(ctx, dpt.alloc(pt.size() * 32));
   TPST_HIP(ctx, ex.alloc(M * 32));
   TPST_HIP(ctx, ey.alloc(Nz * 32));
@@ -932,14 +928,14 @@ extern "C" int tpst_r1cs_is_sat(tpst_ctx* ctx, tpst_r1cs* R, const uint64_t* var
   if (!ctx || !R || !vars || (R->num_inputs && !inputs)) return fail(ctx, TPST_E_ARG, "null argument");
   if (R->owner != ctx) return fail(ctx, TPST_E_ARG, "instance belongs to another context");
   for (size_t i = 0; i < R->num_vars; i++)
-    if (!fr_ok_host(vars + 4 * i)) return fail(ctx, TPST_E_ARG, "witness value >= r");
+    if (!fr_ok(vars + 4 * i)) return fail(ctx, TPST_E_ARG, "witness value >= r");
   for (size_t i = 0; i < R->num_inputs; i++)
-    if (!fr_ok_host(inputs + 4 * i)) return fail(ctx, TPST_E_ARG, "input value >= r");
+    if (!fr_ok(inputs + 4 * i)) return fail(ctx, TPST_E_ARG, "input value >= r");
   std::lock_guard<tpst::CtxMutex> lk(ctx->mu);
   TPST_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const size_t M = R->num_cons, Nz = R->ncols;
-  Buf dvars, dins, z, y[3], flag;
+  DevBuf dvars, dins, z, y[3], flag;
   TPST_HIP(ctx, dvars.alloc(R->num_vars * 32));
   TPST_HIP(ctx, dins.alloc(R->num_inputs * 32 + 32));
   TPST_HIP(ctx, z.alloc(Nz * 32));
@@ -971,8 +967,8 @@ static bool sumcheck_verify(const uint64_t* polys, int NC, int rounds, Fr& e, tp
     Fr at01 = Fr::zero();  // p(0) + p(1) = 2 c_0 + c_1 + ...
     for (int c = 0; c < NC; c++) {
       const uint64_t* w = polys + 4 * ((size_t)j * NC + c);
-      if (!fr_ok_host(w)) return false;
-      cs[c] = frc(w);
+      if (!fr_ok(w)) return false;
+      cs[c] = fr_canon(w);
       at01 = add(at01, cs[c]);
     }
     at01 = add(at01, cs[0]);
@@ -980,7 +976,7 @@ static bool sumcheck_verify(const uint64_t* polys, int NC, int rounds, Fr& e, tp
     for (int c = 0; c < NC; c++) tpst_transcript_append_fr(tr, polys + 4 * ((size_t)j * NC + c));
     uint64_t rc[4];
     tpst_transcript_challenge(tr, rc);
-    rs[j] = frc(rc);
+    rs[j] = fr_canon(rc);
     e = uni_eval(cs, NC, rs[j]);
   }
   return true;
@@ -993,7 +989,7 @@ static int verify_precheck(tpst_ctx* ctx, size_t num_cons, size_t num_vars, size
   const int nvar_bits = log2_exact(num_vars), rx_n = log2_exact(num_cons), ry_n = nvar_bits + 1;
   if (rx_n > TPST_R1CS_MAX_ROUNDS || ry_n > TPST_R1CS_MAX_ROUNDS || nvar_bits > 2 * TPST_MAX_VARS)
     return fail(ctx, TPST_E_ARG, "instance too large for tpst_r1cs_proof");
-  if (tpst_internal_srs_nv(ctx) != nvar_bits - nvar_bits / 2)
+  if (srs_nv(ctx) != nvar_bits - nvar_bits / 2)
     return fail(ctx, TPST_E_STATE, "no SRS loaded for ceil(log2(num_vars) / 2) variables");
   if (proof->rounds_x != rx_n || proof->rounds_y != ry_n || proof->num_vars_log != nvar_bits ||
       proof->open.m_col != nvar_bits / 2 || proof->open.m_row != nvar_bits - nvar_bits / 2)
@@ -1014,9 +1010,9 @@ extern "C" int tpst_r1cs_verify_evals(tpst_ctx* ctx, size_t num_cons, size_t num
   const int rx_n = proof->rounds_x, ry_n = proof->rounds_y, nvar_bits = proof->num_vars_log;
   const auto bad = [&](const char* what) { return fail(ctx, TPST_E_VERIFY, std::string("r1cs verify: ") + what); };
   for (size_t i = 0; i < num_inputs; i++)
-    if (!fr_ok_host(inputs + 4 * i)) return bad("input >= r");
+    if (!fr_ok(inputs + 4 * i)) return bad("input >= r");
   for (int k = 0; k < 3; k++)
-    if (!fr_ok_host(evals + 4 * k)) return bad("matrix evaluation >= r");
+    if (!fr_ok(evals + 4 * k)) return bad("matrix evaluation >= r");
   // 1. the commitment's transcript state, then the inputs (r1csproof.rs:251-262)
   uint64_t c[4];
   tpst_transcript_append_gt(tr, proof->T);
@@ -1028,21 +1024,21 @@ extern "C" int tpst_r1cs_verify_evals(tpst_ctx* ctx, size_t num_cons, size_t num
   std::vector<Fr> tau(rx_n), rx(rx_n), ry(ry_n);
   for (int j = 0; j < rx_n; j++) {
     tpst_transcript_challenge(tr, c);
-    tau[j] = frc(c);
+    tau[j] = fr_canon(c);
   }
   // 3.-4. phase one (degree 3, claim 0); the derived rx is the proof's (constraints.rs:317-319)
   Fr e1 = Fr::zero();
   if (!sumcheck_verify(&proof->sc1[0][0][0], 4, rx_n, e1, tr, rx.data())) return bad("phase-one sum-check round");
   for (int j = 0; j < rx_n; j++) {
     uint64_t w[4];
-    fro(rx[j], w);
+    fr_out(rx[j], w);
     if (memcmp(w, proof->rx[j], 32) != 0) return bad("rx");
   }
   // 5. the phase-one final claim (constraints.rs:328-340)
   Fr cl[4];
   for (int k = 0; k < 4; k++) {
-    if (!fr_ok_host(proof->claims_phase2[k])) return bad("claim >= r");
-    cl[k] = frc(proof->claims_phase2[k]);
+    if (!fr_ok(proof->claims_phase2[k])) return bad("claim >= r");
+    cl[k] = fr_canon(proof->claims_phase2[k]);
   }
   if (!eq(cl[3], mul(cl[0], cl[1]))) return bad("claims_phase2[3] != Az Bz");
   Fr tb = Fr::one();
@@ -1053,27 +1049,28 @@ extern "C" int tpst_r1cs_verify_evals(tpst_ctx* ctx, size_t num_cons, size_t num
   Fr rabc[3];
   for (int k = 0; k < 3; k++) {
     tpst_transcript_challenge(tr, c);
-    rabc[k] = frc(c);
+    rabc[k] = fr_canon(c);
   }
   Fr e2 = add(add(mul(rabc[0], cl[0]), mul(rabc[1], cl[1])), mul(rabc[2], cl[2]));
   if (!sumcheck_verify(&proof->sc2[0][0][0], 3, ry_n, e2, tr, ry.data())) return bad("phase-two sum-check round");
   for (int j = 0; j < ry_n; j++) {
     uint64_t w[4];
-    fro(ry[j], w);
+    fr_out(ry[j], w);
     if (memcmp(w, proof->ry[j], 32) != 0) return bad("ry");
   }
   // 8. z(ry) from the witness evaluation and the sparse (1, inputs)
   //    polynomial (r1csproof.rs:390-398), against the matrix evaluations (:376-388)
-  if (!fr_ok_host(proof->eval_vars_at_ry)) return bad("eval_vars_at_ry >= r");
+  if (!fr_ok(proof->eval_vars_at_ry)) return bad("eval_vars_at_ry >= r");
   Fr io = Fr::zero();
   for (size_t i = 0; i <= num_inputs; i++) {
     Fr chi = Fr::one();
     for (int j = 0; j < nvar_bits; j++)
       chi = mul(chi, ((i >> (nvar_bits - 1 - j)) & 1) ? ry[1 + j] : sub(Fr::one(), ry[1 + j]));
-    io = add(io, i ? mul(chi, frc(inputs + 4 * (i - 1))) : chi);
+    io = add(io, i ? mul(chi, fr_canon(inputs + 4 * (i - 1))) : chi);
   }
-  const Fr zry = add(mul(sub(Fr::one(), ry[0]), frc(proof->eval_vars_at_ry)), mul(ry[0], io));
-  const Fr abc = add(add(mul(rabc[0], frc(evals)), mul(rabc[1], frc(evals + 4))), mul(rabc[2], frc(evals + 8)));
+  const Fr zry = add(mul(sub(Fr::one(), ry[0]), fr_canon(proof->eval_vars_at_ry)), mul(ry[0], io));
+  const Fr abc = add(add(mul(rabc[0], fr_canon(evals)), mul(rabc[1], fr_canon(evals + 4))),
+                     mul(rabc[2], fr_canon(evals + 8)));
   if (!eq(e2, mul(zry, abc))) return bad("phase-two final claim");
   // 9. the transcript state after the sum-checks (:389-395)
   tpst_transcript_challenge(tr, c);
@@ -1090,9 +1087,9 @@ extern "C" int tpst_r1cs_verify(tpst_ctx* ctx, tpst_r1cs* R, const uint64_t* inp
   if (R->owner != ctx) return fail(ctx, TPST_E_ARG, "instance belongs to another context");
   if (int rc = verify_precheck(ctx, R->num_cons, R->num_vars, R->num_inputs, proof)) return rc;
   for (int j = 0; j < proof->rounds_x; j++)
-    if (!fr_ok_host(proof->rx[j])) return fail(ctx, TPST_E_VERIFY, "r1cs verify: rx >= r");
+    if (!fr_ok(proof->rx[j])) return fail(ctx, TPST_E_VERIFY, "r1cs verify: rx >= r");
   for (int j = 0; j < proof->rounds_y; j++)
-    if (!fr_ok_host(proof->ry[j])) return fail(ctx, TPST_E_VERIFY, "r1cs verify: ry >= r");
+    if (!fr_ok(proof->ry[j])) return fail(ctx, TPST_E_VERIFY, "r1cs verify: ry >= r");
   uint64_t evals[12];
   if (int rc = tpst_r1cs_evaluate(ctx, R, &proof->rx[0][0], &proof->ry[0][0], evals)) return rc;
   return tpst_r1cs_verify_evals(ctx, R->num_cons, R->num_vars, inputs, R->num_inputs, evals, tr, proof);
