@@ -507,7 +507,8 @@ int tpst_g1_mul_generator_dev(tpst_ctx* ctx, const void* d_scalars, size_t n, vo
  * kind 0 = Fq Montgomery multiply, 1 = G1 XYZZ mixed add, 2 = Fq inverse, 3 / 4 = Fq multiply
  * variants (two interleaved accumulation chains / independent columns), 5 = G1 XYZZ doubling, 15 = Fq inverse
  * by a whole wave (csrc/inv_wave.h; one chain per 64 threads), 16 + op = one wave
- * running `iters` stages of wave-engine op `op` (csrc/wave_ops.inc).  Runs `threads`
+ * running `iters` stages of wave-engine op `op` (csrc/wave_ops.inc), 13 = G1 XYZZ mixed add
+ * over the radix-2^29 field, 116 = its chain-start form (ZZ = ZZZ = 1).  Runs `threads`
  * threads x `iters` dependent ops each; returns kernel milliseconds. */
 int tpst_microbench(tpst_ctx* ctx, int kind, size_t threads, int iters, double* ms);
 /* shader-clock cycles of the parts of `iters` stages of wave op `op` (forms,

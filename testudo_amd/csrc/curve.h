@@ -106,15 +106,25 @@ TPST_HD Xyzz<F> dbl_affine(const Affine<F>& q) {
   return r;
 }
 
-// madd-2008-s: p + q (q affine)
+// madd-2008-s: p + q (q affine).  `unit` promises that p is infinity or has
+// ZZ = ZZZ = 1 (the second entry of a bucket chain: the first one was copied
+// in), which turns the four products by p.ZZ / p.ZZZ into copies
+// (mmadd-2008-s); the results are canonical either way, so the same words
+// come out.  One body: where `unit` is uniform over the wave (a loop counter)
+// the device code branches around the four products instead of repeating the
+// addition.
 template <class F>
-TPST_HD Xyzz<F> add_affine(const Xyzz<F>& p, const Affine<F>& q) {
+TPST_HD Xyzz<F> add_affine(const Xyzz<F>& p, const Affine<F>& q, bool unit) {
   if (is_inf(q)) return p;
   if (is_zero(p.ZZ)) return {q.x, q.y, F::one(), F::one()};
-  const F U2 = mul(q.x, p.ZZ);
-  const F S2 = mul(q.y, p.ZZZ);
-  const F P = sub(U2, p.X);
-  const F R = sub(S2, p.Y);
+  F P, R;
+  if (unit) {
+    P = sub(q.x, p.X);
+    R = sub(q.y, p.Y);
+  } else {
+    P = sub(mul(q.x, p.ZZ), p.X);
+    R = sub(mul(q.y, p.ZZZ), p.Y);
+  }
   if (is_zero(P)) {
     if (is_zero(R)) return dbl_affine(q);
     return Xyzz<F>::inf();
@@ -125,10 +135,22 @@ TPST_HD Xyzz<F> add_affine(const Xyzz<F>& p, const Affine<F>& q) {
   Xyzz<F> r;
   r.X = sub(sub(sqr(R), PPP), dbl(Q));
   r.Y = mul_sub(R, sub(Q, r.X), p.Y, PPP);
-  r.ZZ = mul(p.ZZ, PP);
-  r.ZZZ = mul(p.ZZZ, PPP);
+  if (unit) {
+    r.ZZ = PP;
+    r.ZZZ = PPP;
+  } else {
+    r.ZZ = mul(p.ZZ, PP);
+    r.ZZZ = mul(p.ZZZ, PPP);
+  }
   return r;
 }
+
+template <class F>
+TPST_HD Xyzz<F> add_affine(const Xyzz<F>& p, const Affine<F>& q) { return add_affine(p, q, false); }
+
+// mmadd-2008-s: p + q for p infinity or with ZZ = ZZZ = 1 (4M + 2S)
+template <class F>
+TPST_HD Xyzz<F> add_affine_unit(const Xyzz<F>& p, const Affine<F>& q) { return add_affine(p, q, true); }
 
 template <class F>
 TPST_HD Xyzz<F> sub_affine(const Xyzz<F>& p, const Affine<F>& q) { return add_affine(p, neg(q)); }

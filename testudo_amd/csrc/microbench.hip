@@ -222,6 +222,22 @@ __global__ void k_mb_madd29(int iters, uint32_t* out) {
   store_f<Fq>(out + 12 * (size_t)t, x);
 }
 
+// kind 116: the chain-start form of the mixed add (add_affine's `unit`: the
+// accumulator has ZZ = ZZZ = 1), same shape as kind 13; only X and Y chain
+__global__ void k_mb_madd29_unit(int iters, uint32_t* out) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  const Affine<Fq29> g = {from_std(Fq::from_limbs(params::G1_GEN_X)), from_std(Fq::from_limbs(params::G1_GEN_Y))};
+  Xyzz<Fq29> acc = dbl_affine(g);
+  acc.X.v[0] ^= (t & 1);
+  for (int i = 0; i < iters; i++) {
+    acc.ZZ = Fq29::one();
+    acc.ZZZ = Fq29::one();
+    acc = add_affine_unit(acc, g);
+  }
+  const Fq x = to_std(add(acc.X, acc.ZZZ));
+  store_f<Fq>(out + 12 * (size_t)t, x);
+}
+
 __global__ void k_mb_dbl(int iters, uint32_t* out) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   G1A g = {Fq::from_limbs(params::G1_GEN_X), Fq::from_limbs(params::G1_GEN_Y)};
@@ -484,6 +500,8 @@ extern "C" int tpst_microbench(tpst_ctx* ctx, int kind, size_t threads, int iter
     k_mb_inv_wave<<<grid_for(threads, 64), 64, 0, ctx->stream>>>(iters, d);
   else if (kind == 13)
     k_mb_madd29<<<grid, bs, 0, ctx->stream>>>(iters, d);
+  else if (kind == 116)
+    k_mb_madd29_unit<<<grid, bs, 0, ctx->stream>>>(iters, d);
   else if (kind == 112)
     k_mb_insn<12><<<grid, bs, 0, ctx->stream>>>(iters, d);
   else if (kind == 113)

@@ -592,6 +592,24 @@ __device__ __forceinline__ Affine<F> fetch_point(const uint32_t* bases, const ui
   return p;
 }
 
+// Chain start: every lane of the accumulation kernels below enters its chunk
+// with acc = infinity and step 0 copies the gathered point in, so at step 1
+// every live lane's accumulator is infinity (an empty or just-closed bucket)
+// or has ZZ = ZZZ = 1 -- for the whole wave, by construction.  That step runs
+// add_affine's `unit` form (curve.h), four products shorter, under a scalar
+// branch on the step counter.  Later bucket starts inside a chunk are per
+// lane and take the full addition.  TPST_CHAIN_UNIT=0 builds the full
+// addition at every step (A/B).
+#ifndef TPST_CHAIN_UNIT
+#define TPST_CHAIN_UNIT 1
+#endif
+#ifndef TPST_K2_LG  // log2 of the window-grouped path's chunk length (A/B)
+#define TPST_K2_LG 4
+#endif
+#ifndef TPST_CHAIN_UNIT_G2  // the G2 pair kernel (k_bucket_acc_short_pair)
+#define TPST_CHAIN_UNIT_G2 TPST_CHAIN_UNIT
+#endif
+
 // Balanced bucket accumulation over the key-sorted entries: thread t owns the
 // chunk of entries [t 2^lg, (t+1) 2^lg).  A bucket lying wholly inside the
 // chunk is stored directly.  A bucket crossing chunk boundaries is finished by
@@ -632,7 +650,8 @@ __global__ void __launch_bounds__(ACC_BLOCK, MINW)
     uint32_t key = keys[c0];
     Affine<C> pt;
     if (key < sent) pt = fetch(vals[c0]);
-    for (size_t e = c0; e < c1; e++) {
+    int step = 0;  // the same in every lane still in the loop
+    for (size_t e = c0; e < c1; e++, step++) {
       uint32_t key_n = sent;
       Affine<C> pt_n;
       if (e + 1 < c1) {
@@ -640,7 +659,7 @@ __global__ void __launch_bounds__(ACC_BLOCK, MINW)
         if (key_n < sent) pt_n = fetch(vals[e + 1]);
       }
       if (key < sent) {
-        acc = add_affine(acc, pt);
+        acc = add_affine(acc, pt, TPST_CHAIN_UNIT && step == 1);
         if (key_n != key) {
           if (bend[key] <= c1) {  // the bucket ends in this chunk
             // began here: complete; began earlier: the chunk's first segment
@@ -751,7 +770,7 @@ __global__ void __launch_bounds__(ACC_BLOCK, MINW)
     if constexpr (NBUF == 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // pt read out of the buffer
     stage_load(NBUF == 1 ? 0 : (int)((s + 1) & 1), val_n, key_n < sent);
     if (live && key < sent) {
-      acc = add_affine(acc, pt);
+      acc = add_affine(acc, pt, TPST_CHAIN_UNIT && s == 1);
       if (key_n != key) {
         if (bend[key] <= c1) {  // the bucket ends in this chunk
           if (bstart[key] >= c0)
@@ -843,7 +862,8 @@ __global__ void __launch_bounds__(64, MINW)
   Affine<C> pt;
   if (key < sent) pt = fetch(vals[c0]);
   Xyzz<C> acc = Xyzz<C>::inf();
-  for (size_t e = c0; e < c1; e++) {
+  int step = 0;  // the same in every lane still in the loop
+  for (size_t e = c0; e < c1; e++, step++) {
     uint32_t key_n = sent;
     Affine<C> pt_n;
     if (e + 1 < c1) {
@@ -851,7 +871,7 @@ __global__ void __launch_bounds__(64, MINW)
       if (key_n < sent) pt_n = fetch(vals[e + 1]);
     }
     if (key < sent) {
-      acc = add_affine(acc, pt);
+      acc = add_affine(acc, pt, TPST_CHAIN_UNIT && step == 1);
       if (key_n != key) {
         const bool starts = bstart[key] >= c0;
         const bool ends = bend[key] <= c1;
@@ -960,7 +980,7 @@ __global__ void __launch_bounds__(64, MINW)
     if constexpr (NBUF == 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // pt read out of the buffer
     stage_load(NBUF == 1 ? 0 : (int)((s + 1) & 1), val_n, key_n < sent);
     if (live && key < sent) {
-      acc = add_affine(acc, pt);
+      acc = add_affine(acc, pt, TPST_CHAIN_UNIT && s == 1);
       if (key_n != key) {
         const bool starts = bstart[key] >= c0;
         const bool ends = bend[key] <= c1;
@@ -1005,7 +1025,8 @@ static __global__ void __launch_bounds__(64, 2)
   Affine<Fq2P> pt;
   if (key < sent) pt = fetch_point_pair(bases, phib, nbase, vals[c0]);
   Xyzz<Fq2P> acc = Xyzz<Fq2P>::inf();
-  for (size_t e = c0; e < c1; e++) {
+  int step = 0;  // the same in every lane still in the loop
+  for (size_t e = c0; e < c1; e++, step++) {
     uint32_t key_n = sent;
     Affine<Fq2P> pt_n;
     if (e + 1 < c1) {
@@ -1013,7 +1034,7 @@ static __global__ void __launch_bounds__(64, 2)
       if (key_n < sent) pt_n = fetch_point_pair(bases, phib, nbase, vals[e + 1]);
     }
     if (key < sent) {
-      acc = add_affine(acc, pt);
+      acc = add_affine(acc, pt, TPST_CHAIN_UNIT_G2 && step == 1);
       if (key_n != key) {
         const bool starts = bstart[key] >= c0;
         const bool ends = bend[key] <= c1;
@@ -1559,7 +1580,9 @@ hipError_t msm_var(Arena& ar, hipStream_t s, const uint32_t* d_bases, const uint
   int lg;
   if (NG > 1) {  // per-group launches: keep >= 4 waves per SIMD in each
     static const size_t simds = device_simds();
-    lg = 4;  // 16-entry chunks: 8 / 32 / 64 measured 4 / 7 / 18 % slower (profiles/r05/g)
+    // 16-entry chunks: 8 / 32 / 64 measured 4 / 7 / 18 % slower (profiles/r05/g);
+    // 8 against 16 again with the chain-start add: profiles/chain_start
+    lg = TPST_K2_LG;
     while (lg < 8 && ((m / NG) >> (lg + 1)) >= (size_t)4 * 64 * simds) lg++;
   } else {
     lg = acc_chunk_lg(m);

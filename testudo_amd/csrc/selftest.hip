@@ -108,9 +108,20 @@ __device__ __forceinline__ Xyzz<T> coop_op(const Xyzz<T>& a, const Xyzz<T>& b) {
     return dbl_quad(a, qi);
 }
 
-template <int FORM, int COP>
+// a lane form's operation: add_affine_unit for the chain-start forms
+template <bool UNIT, int COP, class F>
+__device__ __forceinline__ Xyzz<F> lane_op(const Xyzz<F>& a, const Xyzz<F>& b) {
+  if constexpr (UNIT)
+    return st::curve_op_unit(a, b);
+  else
+    return st::curve_op<COP>(a, b);
+}
+
+template <int OPFORM, int COP>
 __global__ void __launch_bounds__(64) k_selftest_curve(size_t n, const uint32_t* __restrict__ p,
                                                        const uint32_t* __restrict__ q, uint32_t* __restrict__ out) {
+  constexpr bool UNIT = OPFORM >= st::FORM_UNIT;  // FORM_UNIT + a lane form
+  constexpr int FORM = UNIT ? OPFORM - st::FORM_UNIT : OPFORM;
   constexpr bool COOP = FORM == st::FORM_COOP_FQ29_ACC || FORM == st::FORM_COOP_FQ29_PK || FORM == st::FORM_COOP_FQ2_ACC;
   constexpr int T = COOP ? 4 : FORM == st::FORM_PAIR ? 2 : 1;
   const size_t e = ((size_t)blockIdx.x * 64 + threadIdx.x) / T;
@@ -137,7 +148,7 @@ __global__ void __launch_bounds__(64) k_selftest_curve(size_t n, const uint32_t*
       const Xyzz<Fq2P> r = st::curve_op<COP>(load_xyzz_pair(P, i), load_xyzz_pair(Q, i));
       if (live) store_xyzz_pair(O, i, r);
     } else if constexpr (FORM == st::FORM_FQ2) {
-      const Xyzz<Fq2> r = st::curve_op<COP>(load_xyzz(P, i), load_xyzz(Q, i));
+      const Xyzz<Fq2> r = lane_op<UNIT, COP>(load_xyzz(P, i), load_xyzz(Q, i));
       if (store) store_xyzz(O, i, r);
     } else if constexpr (FORM == st::FORM_FQ2_ACC) {  // Fq2x29, converted as the G2 tail kernels do
       const Xyzz<Fq2x29> r = st::curve_op<COP>(load_acc(P, i), load_acc(Q, i));
@@ -151,13 +162,13 @@ __global__ void __launch_bounds__(64) k_selftest_curve(size_t n, const uint32_t*
     const Xyzz<Fq>* Q = reinterpret_cast<const Xyzz<Fq>*>(q);
     Xyzz<Fq>* O = reinterpret_cast<Xyzz<Fq>*>(out);
     if constexpr (FORM == st::FORM_FQ) {
-      const Xyzz<Fq> r = st::curve_op<COP>(load_xyzz(P, i), load_xyzz(Q, i));
+      const Xyzz<Fq> r = lane_op<UNIT, COP>(load_xyzz(P, i), load_xyzz(Q, i));
       if (store) store_xyzz(O, i, r);
     } else if constexpr (FORM == st::FORM_FQ29_ACC) {  // field.h words, converted as the tail kernels do
-      const Xyzz<Fq29> r = st::curve_op<COP>(load_acc(P, i), load_acc(Q, i));
+      const Xyzz<Fq29> r = lane_op<UNIT, COP>(load_acc(P, i), load_acc(Q, i));
       if (store) store_acc(O, i, r);
     } else if constexpr (FORM == st::FORM_FQ29_PK) {  // the accumulation kernels' packed buckets
-      const Xyzz<Fq29> r = st::curve_op<COP>(load_pk(P, i), load_pk(Q, i));
+      const Xyzz<Fq29> r = lane_op<UNIT, COP>(load_pk(P, i), load_pk(Q, i));
       if (store) store_pk(O, i, r);
     } else if constexpr (FORM == st::FORM_COOP_FQ29_ACC) {
       const Xyzz<Fq29> r = coop_op<COP>(load_acc(P, i), load_acc(Q, i));
@@ -189,7 +200,7 @@ extern "C" int tpst_selftest_curve(tpst_ctx* ctx, int op, size_t n, const uint64
   const unsigned grid = grid_for(n * T, 64);
   hipStream_t s = ctx->stream;
 #define TPST_ST_CURVE(F, C) \
-  case F * 16 + C: k_selftest_curve<F, C><<<grid, 64, 0, s>>>(n, d_p, d_q, d_o); break;
+  case (F) * 16 + C: k_selftest_curve<(F), C><<<grid, 64, 0, s>>>(n, d_p, d_q, d_o); break;
 #define TPST_ST_LANE(F)                                                                       \
   TPST_ST_CURVE(F, st::C_ADD_AFFINE) TPST_ST_CURVE(F, st::C_ADD) TPST_ST_CURVE(F, st::C_DBL) \
   TPST_ST_CURVE(F, st::C_DBL_AFFINE) TPST_ST_CURVE(F, st::C_SUB_AFFINE)
@@ -200,6 +211,10 @@ extern "C" int tpst_selftest_curve(tpst_ctx* ctx, int op, size_t n, const uint64
     TPST_ST_LANE(st::FORM_FQ29_ACC) TPST_ST_CURVE(st::FORM_FQ29_ACC, st::C_TO_AFFINE)
     TPST_ST_LANE(st::FORM_FQ29_PK) TPST_ST_CURVE(st::FORM_FQ29_PK, st::C_TO_AFFINE)
     TPST_ST_LANE(st::FORM_FQ2) TPST_ST_CURVE(st::FORM_FQ2, st::C_TO_AFFINE)
+    TPST_ST_CURVE(st::FORM_UNIT + st::FORM_FQ, st::C_ADD_AFFINE)
+    TPST_ST_CURVE(st::FORM_UNIT + st::FORM_FQ29_ACC, st::C_ADD_AFFINE)
+    TPST_ST_CURVE(st::FORM_UNIT + st::FORM_FQ29_PK, st::C_ADD_AFFINE)
+    TPST_ST_CURVE(st::FORM_UNIT + st::FORM_FQ2, st::C_ADD_AFFINE)
     TPST_ST_LANE(st::FORM_FQ2_ACC)
     TPST_ST_LANE(st::FORM_PAIR)
     TPST_ST_COOP(st::FORM_COOP_FQ29_ACC)

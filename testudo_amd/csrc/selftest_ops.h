@@ -143,9 +143,14 @@ enum : int {
   FORM_COOP_FQ29_PK, FORM_FQ2_ACC, N_FORM
 };
 enum : int { C_ADD_AFFINE, C_ADD, C_DBL, C_DBL_AFFINE, C_SUB_AFFINE, C_TO_AFFINE, C_N };
+// chain-start forms: FORM_UNIT + a lane form (FORM_FQ .. FORM_FQ2), C_ADD_AFFINE
+// only, runs add_affine_unit (curve.h) in that form's codec; p must be
+// infinity or have ZZ = ZZZ = 1
+constexpr int FORM_UNIT = 16;
 constexpr int C_GLV_SPLIT = 0;  // FORM_GLV: 8-word canonical scalar in p (q unused) -> k1 | k2
 
 TPST_HD int curve_form(int op) { return op >> 4; }
+TPST_HD bool curve_form_unit(int f) { return f >= FORM_UNIT && f <= FORM_UNIT + FORM_FQ2; }
 TPST_HD bool curve_form_coop(int f) {
   return f == FORM_COOP_FQ29_ACC || f == FORM_COOP_FQ29_PK || f == FORM_COOP_FQ2_ACC;
 }
@@ -155,6 +160,7 @@ TPST_HD bool curve_op_valid(int op) {
   if (op < 0) return false;
   const int f = curve_form(op), i = curve_index(op);
   if (f <= FORM_FQ2) return i < C_N;
+  if (curve_form_unit(f)) return i == C_ADD_AFFINE;
   if (curve_form_coop(f)) return i == C_ADD_AFFINE || i == C_ADD || i == C_DBL;
   if (f == FORM_PAIR || f == FORM_FQ2_ACC) return i <= C_SUB_AFFINE;  // no Fq2P / Fq2x29 inverse: no to_affine
   return f == FORM_GLV && i == C_GLV_SPLIT;
@@ -162,7 +168,7 @@ TPST_HD bool curve_op_valid(int op) {
 
 // u32 words per element of p, q and the result
 TPST_HD int curve_words(int op) {
-  const int f = curve_form(op);
+  const int f = curve_form_unit(curve_form(op)) ? curve_form(op) - FORM_UNIT : curve_form(op);
   const bool g2 = f == FORM_FQ2 || f == FORM_COOP_FQ2_ACC || f == FORM_PAIR || f == FORM_FQ2_ACC;
   return f == FORM_GLV ? 8 : g2 ? 96 : 48;
 }
@@ -184,8 +190,15 @@ TPST_HD Xyzz<F> curve_op(const Xyzz<F>& p, const Xyzz<F>& q) {
     return to_xyzz(to_affine(p));
 }
 
+// the chain-start mixed add in place of C_ADD_AFFINE (FORM_UNIT forms)
 template <class F>
-TPST_HD Xyzz<F> curve_op_rt(int cop, const Xyzz<F>& p, const Xyzz<F>& q) {
+TPST_HD Xyzz<F> curve_op_unit(const Xyzz<F>& p, const Xyzz<F>& q) {
+  return add_affine_unit(p, Affine<F>{q.X, q.Y});
+}
+
+template <class F>
+TPST_HD Xyzz<F> curve_op_rt(int cop, const Xyzz<F>& p, const Xyzz<F>& q, bool unit = false) {
+  if (unit) return curve_op_unit(p, q);
   switch (cop) {
     case C_ADD_AFFINE: return curve_op<C_ADD_AFFINE>(p, q);
     case C_ADD: return curve_op<C_ADD>(p, q);
@@ -215,21 +228,22 @@ TPST_HD void store_xyzz_words(uint32_t* w, const Xyzz<Fq>& v) {
 TPST_HD bool curve_lane_op(int op, const uint32_t* p, const uint32_t* q, uint32_t* out) {
   if (!curve_op_valid(op)) return false;
   const int cop = curve_index(op);
-  switch (curve_form(op)) {
+  const bool unit = curve_form_unit(curve_form(op));
+  switch (unit ? curve_form(op) - FORM_UNIT : curve_form(op)) {
     case FORM_FQ:
-      store_xyzz_words(out, curve_op_rt(cop, load_xyzz_words(p), load_xyzz_words(q)));
+      store_xyzz_words(out, curve_op_rt(cop, load_xyzz_words(p), load_xyzz_words(q), unit));
       return true;
     case FORM_FQ29_ACC: {
       const Xyzz<Fq> a = load_xyzz_words(p), b = load_xyzz_words(q);
       const Xyzz<Fq29> r = curve_op_rt<Fq29>(cop, {from_std(a.X), from_std(a.Y), from_std(a.ZZ), from_std(a.ZZZ)},
-                                             {from_std(b.X), from_std(b.Y), from_std(b.ZZ), from_std(b.ZZZ)});
+                                             {from_std(b.X), from_std(b.Y), from_std(b.ZZ), from_std(b.ZZZ)}, unit);
       store_xyzz_words(out, {to_std(r.X), to_std(r.Y), to_std(r.ZZ), to_std(r.ZZZ)});
       return true;
     }
     case FORM_FQ29_PK: {
       const Xyzz<Fq29> r =
           curve_op_rt<Fq29>(cop, {unpack377(p), unpack377(p + 12), unpack377(p + 24), unpack377(p + 36)},
-                            {unpack377(q), unpack377(q + 12), unpack377(q + 24), unpack377(q + 36)});
+                            {unpack377(q), unpack377(q + 12), unpack377(q + 24), unpack377(q + 36)}, unit);
       pack377(r.X, out);
       pack377(r.Y, out + 12);
       pack377(r.ZZ, out + 24);
@@ -238,7 +252,7 @@ TPST_HD bool curve_lane_op(int op, const uint32_t* p, const uint32_t* q, uint32_
     }
     case FORM_FQ2: {
       const Xyzz<Fq2> r = curve_op_rt<Fq2>(cop, {load_fq2(p), load_fq2(p + 24), load_fq2(p + 48), load_fq2(p + 72)},
-                                           {load_fq2(q), load_fq2(q + 24), load_fq2(q + 48), load_fq2(q + 72)});
+                                           {load_fq2(q), load_fq2(q + 24), load_fq2(q + 48), load_fq2(q + 72)}, unit);
       store_fq2(out, r.X);
       store_fq2(out + 24, r.Y);
       store_fq2(out + 48, r.ZZ);

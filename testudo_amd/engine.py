@@ -242,6 +242,15 @@ SELFTEST_CURVE_FORMS = {"fq": 0, "fq29_acc": 1, "fq29_pk": 2, "fq2": 3, "coop_fq
                         "pair": 6, "glv": 7, "coop_fq29_pk": 8, "fq2_acc": 9}
 SELFTEST_CURVE_OPS = {"add_affine": 0, "add": 1, "dbl": 2, "dbl_affine": 3, "sub_affine": 4, "to_affine": 5}
 SELFTEST_GLV_SPLIT = 7 * 16
+# chain-start forms (add_affine_unit: p infinity or ZZ = ZZZ = 1): form
+# SELFTEST_CURVE_UNIT + a lane form, op add_affine only
+SELFTEST_CURVE_UNIT = 16
+SELFTEST_CURVE_UNIT_FORMS = ("fq", "fq29_acc", "fq29_pk", "fq2")
+
+
+def selftest_curve_unit_op(form: str) -> int:
+    assert form in SELFTEST_CURVE_UNIT_FORMS
+    return (SELFTEST_CURVE_UNIT + SELFTEST_CURVE_FORMS[form]) * 16 + SELFTEST_CURVE_OPS["add_affine"]
 
 
 def selftest_field_words(op: int):
@@ -259,6 +268,8 @@ def selftest_field_words(op: int):
 def selftest_curve_words(op: int) -> int:
     """u32 words per element of p, q and the result of a tpst_selftest_curve op"""
     form = op >> 4
+    if SELFTEST_CURVE_UNIT <= form <= SELFTEST_CURVE_UNIT + 3:
+        form -= SELFTEST_CURVE_UNIT
     return 8 if form == 7 else 96 if form in (3, 5, 6, 9) else 48
 
 

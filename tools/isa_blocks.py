@@ -33,7 +33,13 @@ def blocks(lines):
         if not s or s.startswith(";") or s.startswith("."):
             continue
         if cur is not None:
-            cur[1].append(s.split()[0])
+            op = s.split()[0]
+            cur[1].append(op)
+            if op.startswith("s_cbranch") or op == "s_branch":
+                # the unlabelled fall-through of a branch is a block of its own
+                # (the products a scalar branch skips are priced separately)
+                cur = ["  (fall-through)", []]
+                res.append(cur)
     return res
 
 
