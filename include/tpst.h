@@ -437,6 +437,89 @@ int tpst_r1cs_verify_evals(tpst_ctx* ctx, size_t num_cons, size_t num_vars, cons
 int tpst_r1cs_verify(tpst_ctx* ctx, tpst_r1cs* r1cs, const uint64_t* inputs, tpst_transcript* tr,
                      const tpst_r1cs_proof* proof);
 
+/* ---- Hyrax evaluation proofs (csrc/hyrax.hip) -------------------------------
+ * PolyEvalProof (dense_mlpoly.rs:473-575) over DotProductProofLog
+ * (nizk/mod.rs:32-180) and BulletReductionProof (nizk/bullet.rs): the opening
+ * of the Hyrax commitments of tpst_pedersen_commit_rows / tpst_r1cs_commit.
+ *
+ * These proofs run over PoseidonTranscript<Fr> (poseidon_transcript.rs), the
+ * sponge of MultiCommitGens::new -- not the Fq sponge of tpst_transcript.
+ * state = capacity || rate (3 canonical Fr).  Host only, no context;
+ * TPST_E_ARG for a null pointer, a value >= r or a non-canonical point. */
+typedef struct {
+  uint64_t state[3][4];
+  uint32_t squeezing; /* 0 = absorbing, 1 = squeezing */
+  uint32_t index;     /* next absorb / squeeze position in the rate */
+} tpst_transcript_fr;
+void tpst_transcript_fr_init(tpst_transcript_fr* t);
+/* append_scalar (poseidon_transcript.rs:73-75): one native absorb */
+int tpst_transcript_fr_append_scalar(tpst_transcript_fr* t, const uint64_t* fr);
+/* append_scalar_vector (:88-96): n absorbs of one element each */
+int tpst_transcript_fr_append_scalars(tpst_transcript_fr* t, const uint64_t* fr, size_t n);
+/* append_point (:77-86): the 48 Compress::Yes bytes absorbed as a Vec<u8> */
+int tpst_transcript_fr_append_point(tpst_transcript_fr* t, const uint64_t* g1);
+/* append_bytes (:69-71): u64 length prefix, then 31-byte chunks */
+int tpst_transcript_fr_append_bytes(tpst_transcript_fr* t, const uint8_t* bytes, size_t n);
+/* challenge_scalar (:30-32): squeeze_field_elements(1) */
+int tpst_transcript_fr_challenge(tpst_transcript_fr* t, uint64_t* out_fr);
+
+/* Generators = PolyCommitmentGens::setup(num_vars, label) (dense_mlpoly.rs:
+ * 185-187) = DotProductProofGens::new(R, label), R = 2^(ell - ell/2):
+ * MultiCommitGens::new(R + 1, label) split at R -- `gens` a generator set over
+ * G[0..R) with h (tpst_gens_new(R + 1) then tpst_gens_load of the first R),
+ * Q = G[R] canonical affine (gens_1.G[0]).
+ *
+ * rnd: the reference's thread_rng draws, 3 + 4 log2(n) canonical Fr in draw
+ * order: d, r_delta, r_beta, then 2 log2(n) pairs (blind_L, blind_R) -- the
+ * reference draws twice the pairs it uses (nizk/mod.rs:65); round k consumes
+ * pair k, the rest are only range-checked.
+ *
+ * Errors.  TPST_E_ARG: a null argument, a value >= r, gens->n not a power of
+ * two <= 2^16 (or != R for the evaluation calls), a generator set of another
+ * context.  TPST_E_STATE: a generator set without h.  Verifiers return
+ * TPST_E_VERIFY for a failed equation, rounds != log2(n), a zero challenge, or
+ * any proof or commitment element that is non-canonical, off the curve or
+ * outside the subgroup (checked before the transcript absorbs anything).
+ * `tr` is updated in place. */
+#define TPST_HYRAX_MAX_ROUNDS 16
+/* DotProductProofLog { BulletReductionProof { L_vec, R_vec }, delta, beta, z1, z2 } */
+typedef struct {
+  int32_t rounds, pad;
+  uint64_t L[TPST_HYRAX_MAX_ROUNDS][12], R[TPST_HYRAX_MAX_ROUNDS][12];
+  uint64_t delta[12], beta[12], z1[4], z2[4];
+} tpst_dotprod_proof;
+/* DotProductProofLog::prove (nizk/mod.rs:45-125): x, a = n = gens->n canonical
+ * Fr (n = 1: zero rounds); returns Cx = commit(x, blind_x), Cy = y Q + blind_y h */
+int tpst_dotprod_prove(tpst_ctx* ctx, const tpst_gens* gens, const uint64_t* Q, const uint64_t* x,
+                       const uint64_t* blind_x, const uint64_t* a, const uint64_t* y, const uint64_t* blind_y,
+                       const uint64_t* rnd, tpst_transcript_fr* tr, tpst_dotprod_proof* proof, uint64_t* Cx,
+                       uint64_t* Cy);
+/* DotProductProofLog::verify (nizk/mod.rs:127-179) */
+int tpst_dotprod_verify(tpst_ctx* ctx, const tpst_gens* gens, const uint64_t* Q, const uint64_t* a,
+                        const uint64_t* Cx, const uint64_t* Cy, tpst_transcript_fr* tr,
+                        const tpst_dotprod_proof* proof);
+/* PolyEvalProof::prove (dense_mlpoly.rs:482-534): Z = 2^ell canonical Fr
+ * (1 <= ell <= 32), blinds = 2^(ell/2) Fr or NULL (zero), r = ell Fr
+ * (MSB-first), blind_Zr may be NULL (zero); returns C_Zr'.  _dev: d_Z on the
+ * context's device, ordered after the work queued on tpst_stream. */
+int tpst_hyrax_eval_prove(tpst_ctx* ctx, const tpst_gens* gens, const uint64_t* Q, const uint64_t* Z, int ell,
+                          const uint64_t* blinds, const uint64_t* r, const uint64_t* Zr, const uint64_t* blind_Zr,
+                          const uint64_t* rnd, tpst_transcript_fr* tr, tpst_dotprod_proof* proof, uint64_t* C_Zr);
+int tpst_hyrax_eval_prove_dev(tpst_ctx* ctx, const tpst_gens* gens, const uint64_t* Q, const void* d_Z, int ell,
+                              const uint64_t* blinds, const uint64_t* r, const uint64_t* Zr,
+                              const uint64_t* blind_Zr, const uint64_t* rnd, tpst_transcript_fr* tr,
+                              tpst_dotprod_proof* proof, uint64_t* C_Zr);
+/* PolyEvalProof::verify (dense_mlpoly.rs:536-560): comm = the 2^(ell/2) row
+ * commitments; verify_plain (:562-574): C_Zr = Zr Q */
+int tpst_hyrax_eval_verify(tpst_ctx* ctx, const tpst_gens* gens, const uint64_t* Q, int ell, const uint64_t* r,
+                           const uint64_t* C_Zr, const uint64_t* comm, tpst_transcript_fr* tr,
+                           const tpst_dotprod_proof* proof);
+int tpst_hyrax_eval_verify_plain(tpst_ctx* ctx, const tpst_gens* gens, const uint64_t* Q, int ell, const uint64_t* r,
+                                 const uint64_t* Zr, const uint64_t* comm, tpst_transcript_fr* tr,
+                                 const tpst_dotprod_proof* proof);
+/* DensePolynomial::evaluate (dense_mlpoly.rs:408-414) on the device */
+int tpst_dense_evaluate(tpst_ctx* ctx, const uint64_t* Z, int ell, const uint64_t* r, uint64_t* out_fr);
+
 /* ---- Groth16 over BLS12-377 (csrc/groth16.hip) ----
  * The prover behind R1CSProof::prove_verifier (r1csproof.rs:374-434,
  * Groth16::<E>::prove at :421): ark-groth16 create_proof with the
@@ -529,7 +612,9 @@ int tpst_selftest_curve(tpst_ctx* ctx, int op, size_t n, const uint64_t* p, cons
 /* Per-stage HIP-event timing of the MSM pipeline on the context's stream.
  * stage: 0 decompose, 1 sort, 2 bucket bounds, 3 bucket accumulation (the
  * dominant kernel), 4 bucket reduction, 5 window combine, 6 K1 row sort;
- * 15 / 16: tpst_r1cs_evaluate's eq tables / its reduction and partial sum. */
+ * 15 / 16: tpst_r1cs_evaluate's eq tables / its reduction and partial sum;
+ * 17 / 18 / 19: tpst_hyrax_eval_prove's eq tables / bound / dot-product proof
+ * (first launch to last result, the host work between launches included). */
 int tpst_profile_enable(tpst_ctx* ctx, int on);
 int tpst_profile_reset(tpst_ctx* ctx);
 int tpst_profile_read(tpst_ctx* ctx, int stage, double* total_ms, uint64_t* launches);

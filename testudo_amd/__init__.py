@@ -6,3 +6,5 @@ reference's sqrt-PST surface (``Polynomial.from_evaluations / commit / open /
 verify``, sqrt_pst.rs:14-265).
 """
 from .engine import Context, Gens, TpstError  # noqa: F401
+from .hyrax import (DotProductProof, FrTranscript, HyraxGens, dense_evaluate, dotprod_prove,  # noqa: F401
+                    dotprod_verify, eval_prove, eval_verify, eval_verify_plain)

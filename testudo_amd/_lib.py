@@ -107,6 +107,22 @@ PROTOTYPES = [
     ("tpst_r1cs_is_sat", C.c_int, [_vp, _vp, _u64p, _u64p]),
     ("tpst_r1cs_verify_evals", C.c_int, [_vp, _sz, _sz, _u64p, _sz, _u64p, _vp, _vp]),
     ("tpst_r1cs_verify", C.c_int, [_vp, _vp, _u64p, _vp, _vp]),
+    ("tpst_transcript_fr_init", None, [_vp]),
+    ("tpst_transcript_fr_append_scalar", C.c_int, [_vp, _u64p]),
+    ("tpst_transcript_fr_append_scalars", C.c_int, [_vp, _u64p, _sz]),
+    ("tpst_transcript_fr_append_point", C.c_int, [_vp, _u64p]),
+    ("tpst_transcript_fr_append_bytes", C.c_int, [_vp, C.c_char_p, _sz]),
+    ("tpst_transcript_fr_challenge", C.c_int, [_vp, _u64p]),
+    ("tpst_dotprod_prove", C.c_int, [_vp, _vp, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p, _vp, _vp, _u64p,
+                                     _u64p]),
+    ("tpst_dotprod_verify", C.c_int, [_vp, _vp, _u64p, _u64p, _u64p, _u64p, _vp, _vp]),
+    ("tpst_hyrax_eval_prove", C.c_int, [_vp, _vp, _u64p, _u64p, C.c_int, _u64p, _u64p, _u64p, _u64p, _u64p, _vp, _vp,
+                                        _u64p]),
+    ("tpst_hyrax_eval_prove_dev", C.c_int, [_vp, _vp, _u64p, _vp, C.c_int, _u64p, _u64p, _u64p, _u64p, _u64p, _vp,
+                                            _vp, _u64p]),
+    ("tpst_hyrax_eval_verify", C.c_int, [_vp, _vp, _u64p, C.c_int, _u64p, _u64p, _u64p, _vp, _vp]),
+    ("tpst_hyrax_eval_verify_plain", C.c_int, [_vp, _vp, _u64p, C.c_int, _u64p, _u64p, _u64p, _vp, _vp]),
+    ("tpst_dense_evaluate", C.c_int, [_vp, _u64p, C.c_int, _u64p, _u64p]),
     ("tpst_groth16_setup", C.c_int, [_vp, _vp, _u64p, C.POINTER(_vp)]),
     ("tpst_groth16_pk_free", None, [_vp]),
     ("tpst_groth16_domain", C.c_int, [_vp, C.POINTER(_sz)]),
@@ -179,6 +195,25 @@ class R1CSProof(C.Structure):
         ("transcript_sat_state", C.c_uint64 * 4),
         ("eval_vars_at_ry", C.c_uint64 * 4),
         ("open", OpenProof),
+    ]
+
+
+HYRAX_MAX_ROUNDS = 16
+
+
+class TranscriptFr(C.Structure):
+    """tpst_transcript_fr: PoseidonTranscript<Fr> sponge state."""
+    _fields_ = [("state", (C.c_uint64 * 4) * 3), ("squeezing", C.c_uint32), ("index", C.c_uint32)]
+
+
+class DotProdProof(C.Structure):
+    """tpst_dotprod_proof: DotProductProofLog (nizk/mod.rs:32-38)."""
+    _fields_ = [
+        ("rounds", C.c_int32), ("pad", C.c_int32),
+        ("L", (C.c_uint64 * 12) * HYRAX_MAX_ROUNDS),
+        ("R", (C.c_uint64 * 12) * HYRAX_MAX_ROUNDS),
+        ("delta", C.c_uint64 * 12), ("beta", C.c_uint64 * 12),
+        ("z1", C.c_uint64 * 4), ("z2", C.c_uint64 * 4),
     ]
 
 

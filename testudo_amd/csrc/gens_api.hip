@@ -14,23 +14,10 @@
 #include "../../include/tpst.h"
 #include "ctx.h"
 #include "device_util.h"
+#include "gens_state.h"
 #include "pst_kernels.h"
 
 using namespace tpst;
-
-struct tpst_gens {
-  tpst_ctx* ctx = nullptr;
-  size_t n = 0;
-  bool has_h = false;
-  uint32_t* d_G = nullptr;   // n affine G1, Montgomery
-  uint32_t* d_h = nullptr;   // 1 affine G1, Montgomery
-  BatchTables tables;        // K1 window tables over G
-  ~tpst_gens() {
-    if (d_G) (void)hipFree(d_G);
-    if (d_h) (void)hipFree(d_h);
-    batch_tables_free(tables);
-  }
-};
 
 namespace {
 

@@ -33,6 +33,9 @@ enum MsmStage {
   ST_DECOMPOSE = 0, ST_SORT, ST_BOUNDS, ST_BUCKET_ACC, ST_REDUCE, ST_COMBINE, ST_BATCH_SORT,
   ST_BUILD_Q, ST_SQRT_COMMIT, ST_COMM_LIST, ST_IPP, ST_SQRT_OPEN, ST_MSM_U, ST_MIPP_PROVE, ST_PST_OPEN,
   ST_R1CS_EVAL_EQ, ST_R1CS_EVAL,  // tpst_r1cs_evaluate: the two eq tables; the reduction and its partial sum
+  // tpst_hyrax_eval_prove: the L / R eq tables; bound (partials and their sum); the dot-product proof from its
+  // first launch to the last round's results (the host's transcript and point work between launches included)
+  ST_HYRAX_EQ, ST_HYRAX_BOUND, ST_HYRAX_ROUNDS,
   N_STAGES
 };
 

@@ -111,7 +111,9 @@ class Context:
               # sqrt-PST stages under the reference's Timer labels (sqrt_pst.rs:33-262), device spans
               "build_q", "sqrt_commit", "comm_list", "ipp", "sqrt_open", "msm", "mipp_prove", "pst_open",
               # tpst_r1cs_evaluate: the two eq tables; the reduction kernel and its partial sum
-              "r1cs_eval_eq", "r1cs_eval")
+              "r1cs_eval_eq", "r1cs_eval",
+              # tpst_hyrax_eval_prove: the L / R eq tables; bound; the dot-product proof (host work included)
+              "hyrax_eq", "hyrax_bound", "hyrax_rounds")
 
     def profile(self, on: bool):
         self.check(self.lib.tpst_profile_enable(self.h, 1 if on else 0), "tpst_profile_enable")
