@@ -1,5 +1,5 @@
 """G1 MSMs whose bucket chains start in every way the accumulation kernels'
-step 1 can meet (msm.hip: the chain-start form of the mixed add runs there,
+step 1 can meet (msm_acc.h: the chain-start form of the mixed add runs there,
 where every live accumulator is infinity or has ZZ = ZZZ = 1), bit-exact
 against the CPU oracle orc.g1_msm:
 

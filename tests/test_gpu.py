@@ -116,7 +116,7 @@ def test_g1_msm_linearity_full_size(ctx, lg):
 
 @pytest.mark.parametrize("case", ["uniform", "clustered", "short", "boolean"])
 def test_g1_msm_window_groups_vs_oracle(ctx, case):
-    """n >= 2^17 takes the window-grouped pipeline (msm.hip msm_groups: per-group
+    """n >= 2^17 takes the window-grouped pipeline (msm_var.h msm_groups: per-group
     accumulation launches, group reductions + doubling chains on aux streams).
     'clustered' puts whole windows into a handful of buckets, so buckets span
     many chunks and the chunks straddling two window groups; its sort bins

@@ -105,7 +105,7 @@ __device__ __forceinline__ void store_acc(Xyzz<F>* p, size_t i, const Xyzz<typen
 }
 
 // Buckets, parked pieces and block partials of the accumulation kernels
-// (written and read only by msm.hip's accumulation / fixup / first reduction
+// (written and read only by the MSM's accumulation / fixup / first reduction
 // kernels): for G1 the accumulation field's own Montgomery values packed bit
 // for bit (field29.h pack377; 12 words per coordinate like field.h, so buffer
 // sizes and the all-zero infinity are unchanged).  The accumulation loops

@@ -1,5 +1,5 @@
 // GLV scalar decomposition on G1 (and, with beta^2, on G2): shared by the
-// variable-base MSM (msm.hip) and the GLV fixed-base tables (fbt.hip).
+// variable-base MSM (msm_sort.h) and the GLV fixed-base tables (fbt.hip).
 #pragma once
 #include "device_util.h"
 

@@ -1,5 +1,14 @@
-// Pippenger multi-scalar multiplication engine for CDNA4 (host-side API of
-// msm.hip).  Two shapes, matching the reference hot loops:
+// Pippenger multi-scalar multiplication engine for CDNA4 (host-side API).
+// Layout of its sources, one header per stage, no preprocessor gates:
+//   msm_common.h  TPST_TRY, grid_for, device_simds, ACC_BLOCK, REC29_WORDS
+//   msm_sort.h    signed digits, the scalar decomposition, the bucket sort
+//   msm_acc.h     bucket accumulation kernels and their fixups
+//   msm_reduce.h  bucket reductions (one- and two-level), the window chain
+//   msm_var.h     msm_var<F> (K2) and the point-format conversions
+//   msm.hip       Arena / Profiler host bodies, window sizes, G1 instantiations
+//   msm_g2.hip    G2 instantiations (out-of-line Fq2 products)
+//   msm_batch.hip K1: window tables, the row sorts, msm_batch
+// Two shapes, matching the reference hot loops:
 //
 //  K2  variable-base MSM  sum_i s_i * P_i            (sqrt_pst.rs:198,
 //      mipp.rs:393, config 2 of BASELINE.json)
@@ -82,8 +91,8 @@ struct Arena {
 };
 
 // Longest variable-base MSM one call accepts: the sort runs over
-// m = 2 W n < 2^31 (key, value) entries (int-sized for hipCUB, u32 bucket
-// bounds).  msm_var returns hipErrorInvalidValue beyond it.
+// m = 2 W n < 2^31 (key, value) entries (u32 bucket bounds).  msm_var returns
+// hipErrorInvalidValue beyond it.
 constexpr size_t MSM_MAX_POINTS = (size_t)1 << 27;
 
 // window size used for a variable-base MSM of n points
@@ -106,7 +115,7 @@ hipError_t msm_var(Arena& ar, hipStream_t s, const uint32_t* d_bases, const uint
 
 // Fixed-base tables for K1: T[w][j] = 2^(c w) * B_j (affine, Montgomery).
 struct BatchTables {
-  uint32_t* d_table = nullptr;  // W * N points T[w][j], 128-byte radix-2^29 records (msm.hip fetch_rec29)
+  uint32_t* d_table = nullptr;  // W * N points T[w][j], 128-byte radix-2^29 records (msm_acc.h fetch_rec29)
   size_t N = 0;
   int c = 0;
   int W = 0;

@@ -4,6 +4,16 @@
 // G2 MSMs run on fixed-base tables, fbt.hip).  Its Fq2 products stay out of
 // line (see field.h): inlined, the XYZZ mixed addition spills ~420 VGPRs and
 // the unit takes ~9 min to compile.
-#define TPST_MSM_G2_ONLY
 #define TPST_FQ2_ATTR __host__ __device__ inline __attribute__((noinline))
-#include "msm.hip"
+#include "msm_var.h"
+
+namespace tpst {
+
+// explicit instantiations (G2)
+template hipError_t msm_var<Fq2>(Arena&, hipStream_t, const uint32_t*, const uint32_t*, size_t, Xyzz<Fq2>*,
+                                 hipStream_t, bool*, hipStream_t);
+template hipError_t points_to_mont<Fq2>(hipStream_t, const uint32_t*, uint32_t*, size_t);
+template hipError_t affine_from_mont<Fq2>(hipStream_t, const uint32_t*, uint32_t*, size_t);
+template hipError_t xyzz_to_affine_canonical<Fq2>(hipStream_t, const Xyzz<Fq2>*, uint32_t*, size_t);
+
+}  // namespace tpst

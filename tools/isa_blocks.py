@@ -21,6 +21,22 @@ def kernel_lines(path, key):
     return out
 
 
+def functions(path):
+    """every function of the file, cut as kernel_lines cuts one: (symbol, lines
+    from its label to its .Lfunc_end), kernel descriptors included"""
+    name, out = None, []
+    for l in open(path):
+        if name is None:
+            m = re.match(r"^(_Z\S+):", l)
+            if not m:
+                continue
+            name, out = m.group(1), []
+        out.append(l.rstrip("\n"))
+        if l.startswith(".Lfunc_end"):
+            yield name, out
+            name = None
+
+
 def blocks(lines):
     res, cur = [], None
     for l in lines:

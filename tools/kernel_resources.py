@@ -6,7 +6,10 @@ AGPRs, SGPRs, VGPR / SGPR spills, private scratch bytes per lane, the
 compiler's occupancy (waves per SIMD) and LDS bytes per workgroup.
 
   python tools/kernel_resources.py [--out profiles/r05/kernel_resources.txt]
-                                   [--only msm.hip,...] [--check]
+                                   [--only msm.hip,msm_batch.hip,...] [--check]
+
+--only takes translation units: msm.hip holds the G1 variable-base MSM's
+kernels (K2), msm_batch.hip the commit's (K1), msm_g2.hip the G2 ones.
 
 --check exits non-zero when a kernel listed in HOT has VGPR spills or private
 scratch (the accumulation / fixup / reduction kernels of the MSMs and the
@@ -34,7 +37,6 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HOT = [
     "k_bucket_acc_short<Fp<FqCfg>, 2, true>",
     "k_bucket_acc_short_lds<2, true>",
-    "k_bucket_acc_chunk<Fp<FqCfg>, 2, true>",
     "k_bucket_acc_chunk_lds<2>",
     "k_bucket_fixup_short<Fp<FqCfg> >",
     "k_bucket_fixup_quad<Fp<FqCfg> >",
@@ -130,7 +132,8 @@ def main() -> int:
             lanes.append("%s (%s)" % (k, r.get("sspill")))
     text = "\n".join(lines) + "\n"
     seen = {short(r["name"]) for r in rows}
-    whole = not a.only or {"msm.hip", "hyrax.hip"} <= set(a.only.split(","))  # every file with a HOT kernel
+    # every file with a HOT kernel (msm.hip: K2; msm_batch.hip: K1 and the reductions both use)
+    whole = not a.only or {"msm.hip", "msm_batch.hip", "hyrax.hip"} <= set(a.only.split(","))
     missing = [h for h in HOT if h not in seen] if whole else []
     if missing:
         text += "\nHOT kernels not found (renamed?):\n" + "\n".join("  " + m for m in missing) + "\n"

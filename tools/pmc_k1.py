@@ -1,5 +1,5 @@
 """Summarise rocprofv3 --pmc passes of tools/prof_open.py 24 (the 2^24
-sqrt-PST commit) for K1's accumulation kernel k_bucket_acc_chunk<Fq> (one
+sqrt-PST commit) for K1's accumulation kernel k_bucket_acc_chunk_lds (one
 launch per commit): HBM / fabric bytes per launch with the gfx950 FETCH_SIZE
 x2 correction (MI355X_MICROARCH.md), VALU instructions per launch, and the
 per-launch duration from a kernel trace of the same script.
@@ -12,7 +12,7 @@ import json
 import os
 import sys
 
-KERNEL = "k_bucket_acc_chunk"
+KERNEL = "k_bucket_acc_chunk"  # substring of k_bucket_acc_chunk_lds (and of earlier profiles' kernel)
 
 
 def values(d, counter):
@@ -37,7 +37,7 @@ def main():
     madds = rows * npts * W          # one table gather + mixed add per (row, point, window) entry
     f_kb, w_kb = avg(fetch), avg(write) or 0.0
     hbm = (2 * f_kb + w_kb) * 1024.0 if f_kb is not None else None
-    res = {"kernel": "k_bucket_acc_chunk<Fq> (K1, 2^24 sqrt-PST commit: 4096 rows x 4096 points, c = 12)",
+    res = {"kernel": "k_bucket_acc_chunk_lds (K1, 2^24 sqrt-PST commit: 4096 rows x 4096 points, c = 12)",
            "launches": len(fetch), "fetch_size_kb_per_launch": f_kb, "write_size_kb_per_launch": w_kb,
            "correction": "FETCH_SIZE x2 (gfx950), WRITE_SIZE as reported; KB = 1024 B",
            "hbm_bytes_per_launch": hbm, "valu_insts_per_launch": avg(valu),

@@ -1,6 +1,6 @@
 """Summarise rocprofv3 --pmc passes of the bench into the roofline's traffic
 and VALU figures for the dominant kernel (k_bucket_acc_short): the MSM runs
-one launch per window group (msm.hip msm_groups), so the figures are per MSM
+one launch per window group (msm_var.h msm_groups), so the figures are per MSM
 = the sum over one call's launches (launch count of the rarest grid = MSMs).  gfx950 corrections (MI355X_MICROARCH.md, HBM section): FETCH_SIZE
 reports half of the bytes of wide coalesced reads -> x2; WRITE_SIZE as is.
 FETCH/WRITE_SIZE are in KB (rocprofv3 derived metrics, 1024 B).
