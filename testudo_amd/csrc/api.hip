@@ -242,7 +242,11 @@ extern "C" int tpst_g2_msm_fixed(tpst_ctx* ctx, const uint64_t* bases, size_t n,
 // ctx->msm_tail, with one of three arenas: call i+1's sort runs under call
 // i's accumulation, its accumulation under call i's tail (with two arenas the
 // sort of call i+1 waited for call i-1's tail, itself stretched by call i's
-// accumulation: 0.85 ms idle between accumulations, profiles/r05/f).  Stream order is kept
+// accumulation: 0.85 ms idle between accumulations, profiles/r05/f).  In that
+// steady state the tail's latency is hidden and its instructions take issue
+// slots from the next accumulation, so a call that finds the previous tail
+// still pending takes the tail forms with the fewest instructions
+// (msm_var's `throughput`; profiles/fixup_order).  Stream order is kept
 // for the caller: each call starts after the work already on ctx->stream (its
 // inputs), the next entry point of any other kind (and tpst_synchronize /
 // tpst_join_stream) first waits for the pending tails (CtxMutex::lock), and a
@@ -285,8 +289,24 @@ static int msm_dev_impl(tpst_ctx* ctx, const void* d_bases, const void* d_scalar
   // n = 0 writes msm_out[k] on bulk without front work: order it after the
   // tail of the call that last used slot k (it may still read msm_out[k])
   if (ctx->msm_done_set[k]) TPST_HIP(ctx, hipStreamWaitEvent(bulk, ctx->msm_done[k], 0));
+  // the regime: a pipelined call that finds the previous call's tail still
+  // pending on the device is in the steady state of back-to-back calls -- its
+  // own tail will run under the next accumulation, so it takes the throughput
+  // forms (msm_var.h).  A first or lone call, and every stream-ordered one,
+  // keeps the latency forms.
+  bool throughput = false;
+  const int prev = (k + tpst_ctx::MSM_SLOTS - 1) % tpst_ctx::MSM_SLOTS;
+  if (async && ctx->msm_done_set[prev]) {
+    const hipError_t q = hipEventQuery(ctx->msm_done[prev]);
+    if (q == hipErrorNotReady) {
+      throughput = true;
+      (void)hipGetLastError();  // an answer, not a failure: do not leave it as the sticky last error
+    } else {
+      TPST_HIP(ctx, q);
+    }
+  }
   TPST_HIP(ctx, msm_var<Fq>(ar, bulk, (const uint32_t*)d_bases, (const uint32_t*)d_scalars, n, d_r, ctx->msm_tail,
-                            &on_tail, front));
+                            &on_tail, front, throughput));
   hipStream_t t = on_tail ? ctx->msm_tail : bulk;
   TPST_HIP(ctx, xyzz_to_affine_canonical<Fq>(t, d_r, (uint32_t*)d_out, 1));
   TPST_HIP(ctx, hipEventRecord(ctx->msm_done[k], t));

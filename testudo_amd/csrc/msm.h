@@ -108,10 +108,14 @@ int msm_window_bits(size_t n);
 // front != nullptr: the scalar decomposition and the sort run on `front`
 // (ordered before s's accumulation by an event) -- so a pipelining caller's
 // next call sorts while this one accumulates.
+// throughput: the call's tail runs under the next call's accumulation (a
+// pipelining caller in its steady state), so the window-grouped G1 MSM takes
+// the tail forms that cost the fewest issue slots instead of the ones that
+// finish a lone call soonest (msm_var.h; TPST_MSM_TAIL overrides).
 template <class F>
 hipError_t msm_var(Arena& ar, hipStream_t s, const uint32_t* d_bases, const uint32_t* d_scalars,
                    size_t n, Xyzz<F>* d_out, hipStream_t tail = nullptr, bool* on_tail = nullptr,
-                   hipStream_t front = nullptr);
+                   hipStream_t front = nullptr, bool throughput = false);
 
 // Fixed-base tables for K1: T[w][j] = 2^(c w) * B_j (affine, Montgomery).
 struct BatchTables {

@@ -1,6 +1,7 @@
 // Bucket accumulation kernels and their fixups (K2 short chunks, K1 long chunks).
 #pragma once
 #include "msm_common.h"
+#include "msm_pieces.h"
 
 namespace tpst {
 
@@ -407,14 +408,11 @@ static __global__ void __launch_bounds__(64, 2)
   }
 }
 
-// Buckets spanning more than LONG_PARTS chunks (many equal digits: small or
-// boolean scalars put most entries of a window into one bucket) are not
-// walked by one lane of the fixups below -- 2^20 entries of one bucket would
-// be a 32 768-add serial chain -- but appended to a per-group list and summed
-// by k_bucket_fixup_long, one workgroup per bucket (strided partial sums, then
-// a tree in LDS).  cap bounds the list: every listed bucket covers more than
-// LONG_PARTS whole chunks of its group's entries.
-constexpr uint32_t LONG_PARTS = 64;
+// The long list (LONG_PARTS, msm_pieces.h): a bucket spanning more than
+// LONG_PARTS chunks is summed by k_bucket_fixup_long, one workgroup per bucket
+// (strided partial sums, then a tree in LDS).  cap bounds the list: every
+// listed bucket covers more than LONG_PARTS whole chunks of its group's
+// entries.  G1: k_fixup_order fills it; G2: the pair fixup.
 constexpr int LONG_THREADS = 256;
 constexpr unsigned LONG_GRID = 32;
 struct LongList {
@@ -438,7 +436,7 @@ __global__ void __launch_bounds__(LONG_THREADS) k_bucket_fixup_long(const uint32
   const uint32_t tid = threadIdx.x;
   for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
     const uint32_t b = ll.list[i];
-    const size_t t0 = (size_t)bstart[b] >> lg, t1 = (size_t)(bend[b] - 1) >> lg;
+    const size_t t0 = (size_t)bstart[b] >> lg, t1 = t0 + fixup_pieces(bstart[b], bend[b], lg);
     Xyzz<C> acc = tid == 0 ? load_pk(part, 2 * t0 + 1) : Xyzz<C>::inf();
     for (size_t t = t0 + 1 + tid; t <= t1; t += LONG_THREADS) acc = add(acc, load_pk(part, 2 * t));
     sh[tid] = acc;
@@ -474,50 +472,104 @@ static __global__ void __launch_bounds__(64, 2)
   store_xyzz_pair(buckets, b, acc);
 }
 
+// G1: the fixup visits a window group's buckets in order of their piece count
+// (fixup_pieces), longest class first, so that the lanes of a wave run the
+// same number of additions: in bucket order a wave of 64 runs to its longest
+// bucket (5.2 additions at the 2^20 shape against a mean of 3.9).  Two small
+// kernels per group, a counting sort over the FIXUP_CLASSES classes of its
+// buckets [b0, b1): k_fixup_hist counts the classes (LDS histogram per
+// workgroup, then hist[class]); k_fixup_order gives every workgroup a run of
+// each class (cur[class]) and writes the bucket indices to order[0 ..), class
+// FIXUP_CAP first.  Buckets with nothing to fix are left out, those of the
+// long list are pushed there.  The order inside a class is whatever the
+// atomics give: each bucket's sum is independent.  hist and cur are zero
+// before the two run.
+constexpr int ORDER_THREADS = 256;
+
+// listed buckets of a group: its classes 1 .. FIXUP_CAP
+__device__ __forceinline__ uint32_t fixup_listed(const uint32_t* __restrict__ hist) {
+  uint32_t n = 0;
+  for (uint32_t k = 1; k < FIXUP_CLASSES; k++) n += hist[k];
+  return n;
+}
+
+static __global__ void __launch_bounds__(ORDER_THREADS)
+    k_fixup_hist(const uint32_t* __restrict__ bstart, const uint32_t* __restrict__ bend, uint32_t b0, uint32_t b1,
+                 int lg, uint32_t* __restrict__ hist) {
+  __shared__ uint32_t h[FIXUP_CLASSES];
+  if (threadIdx.x < FIXUP_CLASSES) h[threadIdx.x] = 0;
+  __syncthreads();
+  const uint32_t b = b0 + blockIdx.x * ORDER_THREADS + threadIdx.x;
+  const uint32_t cls = b < b1 ? fixup_class(fixup_pieces(bstart[b], bend[b], lg)) : 0u;
+  if (cls != 0 && cls != FIXUP_LONG) atomicAdd(&h[cls], 1u);
+  __syncthreads();
+  if (threadIdx.x != 0 && threadIdx.x < FIXUP_CLASSES && h[threadIdx.x]) atomicAdd(&hist[threadIdx.x], h[threadIdx.x]);
+}
+
+static __global__ void __launch_bounds__(ORDER_THREADS)
+    k_fixup_order(const uint32_t* __restrict__ bstart, const uint32_t* __restrict__ bend, uint32_t b0, uint32_t b1,
+                  int lg, const uint32_t* __restrict__ hist, uint32_t* __restrict__ cur,
+                  uint32_t* __restrict__ order, LongList ll) {
+  __shared__ uint32_t h[FIXUP_CLASSES], base[FIXUP_CLASSES];
+  if (threadIdx.x < FIXUP_CLASSES) h[threadIdx.x] = 0;
+  __syncthreads();
+  const uint32_t b = b0 + blockIdx.x * ORDER_THREADS + threadIdx.x;
+  const uint32_t cls = b < b1 ? fixup_class(fixup_pieces(bstart[b], bend[b], lg)) : 0u;
+  uint32_t r = 0;
+  if (cls == FIXUP_LONG)
+    ll.push(b);
+  else if (cls != 0)
+    r = atomicAdd(&h[cls], 1u);
+  __syncthreads();
+  if (threadIdx.x != 0 && threadIdx.x < FIXUP_CLASSES) {
+    uint32_t off = 0;  // the longer classes come first
+    for (uint32_t k = FIXUP_CAP; k > threadIdx.x; k--) off += hist[k];
+    base[threadIdx.x] = off + (h[threadIdx.x] ? atomicAdd(&cur[threadIdx.x], h[threadIdx.x]) : 0u);
+  }
+  __syncthreads();
+  // base + r < the group's listed buckets <= b1 - b0: both kernels class the same bounds
+  if (cls != 0 && cls != FIXUP_LONG) order[base[cls] + r] = b;
+}
+
 // buckets crossing chunk boundaries: trailing piece of the first chunk plus
-// the leading pieces of the following ones
+// the leading pieces of the following ones.  Lane i finishes bucket order[i]
+// of its group's listed buckets (hist: the group's class counts); the grid
+// covers the group's buckets, waves past the listed ones exit at once.
 template <class F>
 __global__ void __launch_bounds__(64, (sizeof(F) > 48 ? 1 : 2))
-    k_bucket_fixup_short(const uint32_t* __restrict__ bstart, const uint32_t* __restrict__ bend, size_t b0,
-                         size_t b1, int lg, const Xyzz<F>* __restrict__ part, Xyzz<F>* __restrict__ buckets,
-                         int prio, LongList ll) {
+    k_bucket_fixup_short(const uint32_t* __restrict__ bstart, const uint32_t* __restrict__ bend,
+                         const uint32_t* __restrict__ order, const uint32_t* __restrict__ hist, int lg,
+                         const Xyzz<F>* __restrict__ part, Xyzz<F>* __restrict__ buckets, int prio) {
   using C = typename AccField<F>::T;
   set_wave_prio(prio);
-  const size_t b = b0 + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= b1) return;
-  const uint32_t s = bstart[b], e = bend[b];
-  if (e <= s) return;
-  const size_t t0 = (size_t)s >> lg, t1 = (size_t)(e - 1) >> lg;
-  if (t0 == t1) return;
-  if (t1 - t0 > LONG_PARTS) {
-    ll.push((uint32_t)b);
-    return;
-  }
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= fixup_listed(hist)) return;
+  const uint32_t b = order[i];
+  const uint32_t s = bstart[b];
+  const size_t t0 = (size_t)s >> lg, t1 = t0 + fixup_pieces(s, bend[b], lg);
   Xyzz<C> acc = load_pk(part, 2 * t0 + 1);
   for (size_t t = t0 + 1; t <= t1; t++) acc = add(acc, load_pk(part, 2 * t));
   store_pk(buckets, b, acc);
 }
 
 // the same fixup, one quad of lanes per bucket (coop.h: 4 product latencies
-// per addition instead of ~14): for the last window group, whose fixup sits on
-// the MSM's tail with one lone lane per bucket at ~2 waves per CU
+// per addition instead of ~14): for the last window group of a lone call,
+// whose fixup sits on the MSM's tail with one lone lane per bucket at ~2
+// waves per CU
 template <class F>
 __global__ void __launch_bounds__(64) k_bucket_fixup_quad(const uint32_t* __restrict__ bstart,
-                                                          const uint32_t* __restrict__ bend, size_t b0, size_t b1,
-                                                          int lg, const Xyzz<F>* __restrict__ part,
-                                                          Xyzz<F>* __restrict__ buckets, LongList ll) {
+                                                          const uint32_t* __restrict__ bend,
+                                                          const uint32_t* __restrict__ order,
+                                                          const uint32_t* __restrict__ hist, int lg,
+                                                          const Xyzz<F>* __restrict__ part,
+                                                          Xyzz<F>* __restrict__ buckets) {
   using C = typename AccField<F>::T;
-  const size_t b = b0 + (((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 2);
+  const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 2;
   const int qi = threadIdx.x & 3;
-  if (b >= b1) return;  // quad-uniform
-  const uint32_t s = bstart[b], e = bend[b];
-  if (e <= s) return;
-  const size_t t0 = (size_t)s >> lg, t1 = (size_t)(e - 1) >> lg;
-  if (t0 == t1) return;
-  if (t1 - t0 > LONG_PARTS) {
-    if (qi == 0) ll.push((uint32_t)b);
-    return;
-  }
+  if (i >= fixup_listed(hist)) return;  // quad-uniform
+  const uint32_t b = order[i];
+  const uint32_t s = bstart[b];
+  const size_t t0 = (size_t)s >> lg, t1 = t0 + fixup_pieces(s, bend[b], lg);
   Xyzz<C> acc = load_pk(part, 2 * t0 + 1);
   for (size_t t = t0 + 1; t <= t1; t++) acc = add_quad(acc, load_pk(part, 2 * t), qi);
   if (qi == 0) store_pk(buckets, b, acc);

@@ -11,7 +11,7 @@ namespace tpst {
 
 // explicit instantiations (G2)
 template hipError_t msm_var<Fq2>(Arena&, hipStream_t, const uint32_t*, const uint32_t*, size_t, Xyzz<Fq2>*,
-                                 hipStream_t, bool*, hipStream_t);
+                                 hipStream_t, bool*, hipStream_t, bool);
 template hipError_t points_to_mont<Fq2>(hipStream_t, const uint32_t*, uint32_t*, size_t);
 template hipError_t affine_from_mont<Fq2>(hipStream_t, const uint32_t*, uint32_t*, size_t);
 template hipError_t xyzz_to_affine_canonical<Fq2>(hipStream_t, const Xyzz<Fq2>*, uint32_t*, size_t);

@@ -1,6 +1,8 @@
 // The variable-base MSM driver (msm_var<F>) and the point-format conversions;
 // instantiated for G1 in msm.hip and for G2 in msm_g2.hip.
 #pragma once
+#include <cstdio>
+#include <cstring>
 #include "msm_sort.h"
 #include "msm_acc.h"
 #include "msm_reduce.h"
@@ -82,7 +84,9 @@ hipError_t xyzz_to_affine_canonical(hipStream_t s, const Xyzz<F>* d_in, uint32_t
 }
 
 // the last window group's fixup (on the MSM's tail) runs one quad of lanes
-// per bucket; the aux-stream groups one lane per bucket at s_setprio 2
+// per bucket in a lone call; the aux-stream groups one lane per bucket at
+// s_setprio 2 (priority 0 there measured slower and erratic, 298-310 against
+// 311 Mscalar/s: profiles/fixup_order)
 constexpr int RED_PRIO = 2;
 
 // window groups of the variable-base MSM (3; sweep of 1-5 in
@@ -113,9 +117,30 @@ static void msm_group_bounds(int W, int NG, int* wb) {
   }
 }
 
+// TPST_MSM_TAIL=auto|latency|throughput (read once per process): which tail
+// forms the window-grouped G1 MSM takes.  auto (the default): msm_var's
+// `throughput` argument, i.e. the caller's regime; the other two force one
+// set for every call (A/B, tests).  0 auto, 1 latency, 2 throughput.
+static int msm_tail_mode() {
+  static const int mode = [] {
+    const char* e = getenv("TPST_MSM_TAIL");
+    if (e && !strcmp(e, "latency")) return 1;
+    if (e && !strcmp(e, "throughput")) return 2;
+    return 0;
+  }();
+  return mode;
+}
+
+// TPST_MSM_TAIL_TRACE=1 (diagnostics): one stderr line per window-grouped G1
+// MSM naming the tail forms it took
+static void msm_tail_trace(bool grouped, bool throughput, size_t n) {
+  static const bool on = getenv("TPST_MSM_TAIL_TRACE") != nullptr;
+  if (on && grouped) fprintf(stderr, "msm tail %s n=%zu\n", throughput ? "throughput" : "latency", n);
+}
+
 template <class F>
 hipError_t msm_var(Arena& ar, hipStream_t s, const uint32_t* d_bases, const uint32_t* d_scalars, size_t n,
-                   Xyzz<F>* d_out, hipStream_t tail, bool* on_tail, hipStream_t front) {
+                   Xyzz<F>* d_out, hipStream_t tail, bool* on_tail, hipStream_t front, bool throughput) {
   if (on_tail) *on_tail = false;
   if (n == 0) {
     Xyzz<F> inf = Xyzz<F>::inf();
@@ -138,6 +163,16 @@ hipError_t msm_var(Arena& ar, hipStream_t s, const uint32_t* d_bases, const uint
   SortPlan sp;
   if (!sort_plan(sent, n, m, sp)) return hipErrorInvalidValue;
   const int NG = msm_groups(n, W);
+  // Tail forms (G1, window groups).  Latency: what finishes a lone call
+  // soonest -- group 0's fixup and group 1's reduction on quads of lanes.
+  // Throughput: the call's tail runs under the next call's accumulation, its
+  // latency is hidden and its instructions take issue slots from that
+  // accumulation -- both run one lane per bucket / segment (the quad forms
+  // cost 1.7x / 2x the instructions).  A/Bs of these two and of the members
+  // that lost (group 0's reduction two-level, aux priority 0, two groups):
+  // profiles/fixup_order.
+  const bool tp = g1 && NG > 1 && (msm_tail_mode() == 2 || (msm_tail_mode() == 0 && throughput));
+  msm_tail_trace(g1 && NG > 1, tp, n);
   int wb[Arena::N_AUX_EV / 2 + 1];
   msm_group_bounds(W, NG, wb);
   if (NG > 1) TPST_TRY(ar.aux_init());
@@ -162,7 +197,8 @@ hipError_t msm_var(Arena& ar, hipStream_t s, const uint32_t* d_bases, const uint
                 Arena::need(W, sizeof(Xyzz<F>)) + Arena::need(NG, sizeof(Xyzz<F>)) + Arena::need(W + 1, 4) +
                 Arena::need(glv && !rec29 ? n * PW : 1, 4) + Arena::need(rec29 ? 2 * n * REC29_WORDS : 1, 4) +
                 Arena::need((size_t)sp.ntile * sp.nbins, 4) +
-                Arena::need(sp.nbins, 4) + Arena::need(sp.nbins + 1, 4) + Arena::need(NG, 4) +
+                Arena::need(sp.nbins, 4) + Arena::need(sp.nbins + 1, 4) +
+                Arena::need((size_t)NG * (1 + 2 * FIXUP_CLASSES), 4) + Arena::need(g1 ? nbk : 1, 4) +
                 Arena::need((size_t)NG * (m / ((size_t)LONG_PARTS << lg) + 1), 4) + 8192;
   ar.reset();
   TPST_TRY(ar.reserve(need));
@@ -188,7 +224,13 @@ hipError_t msm_var(Arena& ar, hipStream_t s, const uint32_t* d_bases, const uint
   // LONG_PARTS << lg entries, and buckets are disjoint: at most m / (LONG_PARTS
   // << lg) of them in any group (the list can never overflow)
   const uint32_t lcap = (uint32_t)(m / ((size_t)LONG_PARTS << lg)) + 1;
-  uint32_t* lcnt = ar.take<uint32_t>(NG);
+  // zeroed per call: the long lists' counts, then (G1) the fixup order's
+  // class counts and cursors of every group
+  const size_t nmeta = (size_t)NG * (1 + 2 * FIXUP_CLASSES);
+  uint32_t* lcnt = ar.take<uint32_t>(nmeta);
+  uint32_t* fhist = lcnt + NG;
+  uint32_t* fcur = fhist + (size_t)NG * FIXUP_CLASSES;
+  uint32_t* order = ar.take<uint32_t>(g1 ? nbk : 1);  // group g's listed buckets at order[wb[g] nb ..)
   uint32_t* llist = ar.take<uint32_t>((size_t)NG * lcap);
 
   Profiler* pf = ar.prof;
@@ -196,7 +238,7 @@ hipError_t msm_var(Arena& ar, hipStream_t s, const uint32_t* d_bases, const uint
   if (!pf) pf = &dummy;
   const hipStream_t fs = front ? front : s;
   pf->begin(ST_DECOMPOSE, fs);
-  TPST_TRY(hipMemsetAsync(lcnt, 0, NG * sizeof(uint32_t), fs));
+  TPST_TRY(hipMemsetAsync(lcnt, 0, nmeta * sizeof(uint32_t), fs));
   k_decompose_hist<F><<<sp.ntile, SORT_THREADS, sp.nbins * 4, fs>>>(d_scalars, n, c, W, glv ? 1 : 0, sent, sp.lo,
                                                                   sp.nbins, sp.tile, keys, vals, tab, d_bases, phib,
                                                                   rec);
@@ -276,28 +318,52 @@ hipError_t msm_var(Arena& ar, hipStream_t s, const uint32_t* d_bases, const uint
     if (g == 0) pf->end(ST_BUCKET_ACC, bulk);
     const size_t b0 = (size_t)wlo * nb, b1 = (size_t)whi * nb;
     hipStream_t a = g ? ar.aux[g % Arena::N_AUX] : t0;
+    const LongList ll{lcnt + g, llist + (size_t)g * lcap, lcap};
+    uint32_t* const ghist = fhist + g * FIXUP_CLASSES;
+    // G1: the group's fixup order and long list (msm_acc.h), on the group's own
+    // stream.  With the sort on `front` they wait for the sort alone and run
+    // beside the accumulation; otherwise they follow it.  (On `front` itself
+    // they cost the pipelined MSM 0.6 %: two more launches in the chain of
+    // low-priority sort kernels that the next accumulation waits for;
+    // profiles/fixup_order.)
+    const auto fixup_order = [&]() -> hipError_t {
+      if constexpr (g1) {
+        const unsigned grid = grid_for(b1 - b0, ORDER_THREADS);
+        k_fixup_hist<<<grid, ORDER_THREADS, 0, a>>>(bstart, bend, (uint32_t)b0, (uint32_t)b1, lg, ghist);
+        TPST_TRY(hipGetLastError());
+        k_fixup_order<<<grid, ORDER_THREADS, 0, a>>>(bstart, bend, (uint32_t)b0, (uint32_t)b1, lg, ghist,
+                                                     fcur + g * FIXUP_CLASSES, order + b0, ll);
+        TPST_TRY(hipGetLastError());
+      }
+      return hipSuccess;
+    };
+    if (fs != s) {
+      TPST_TRY(hipStreamWaitEvent(a, ar.aux_ev[Arena::N_AUX_EV - 1], 0));
+      TPST_TRY(fixup_order());
+    }
     if (NG > 1) {
       TPST_TRY(hipEventRecord(ar.aux_ev[2 * g], bulk));
       TPST_TRY(hipStreamWaitEvent(a, ar.aux_ev[2 * g], 0));
     }
-    const LongList ll{lcnt + g, llist + (size_t)g * lcap, lcap};
+    if (fs == s) TPST_TRY(fixup_order());
     if constexpr (std::is_same<F, Fq2>::value)
       k_bucket_fixup_short_pair<<<grid_for(2 * (b1 - b0), 64), 64, 0, a>>>(bstart, bend, b0, b1, lg, part, buckets,
                                                                           g ? RED_PRIO : 0, ll);
-    else if (g == 0)
-      k_bucket_fixup_quad<F><<<grid_for(4 * (b1 - b0), 64), 64, 0, a>>>(bstart, bend, b0, b1, lg, part, buckets, ll);
+    else if (g == 0 && !tp)
+      k_bucket_fixup_quad<F><<<grid_for(4 * (b1 - b0), 64), 64, 0, a>>>(bstart, bend, order + b0, ghist, lg, part,
+                                                                        buckets);
     else
-      k_bucket_fixup_short<F><<<grid_for(b1 - b0, 64), 64, 0, a>>>(bstart, bend, b0, b1, lg, part, buckets,
-                                                                    RED_PRIO, ll);
+      k_bucket_fixup_short<F><<<grid_for(b1 - b0, 64), 64, 0, a>>>(bstart, bend, order + b0, ghist, lg, part, buckets,
+                                                                    g ? RED_PRIO : 0);
     TPST_TRY(hipGetLastError());
     k_bucket_fixup_long<F><<<LONG_GRID, LONG_THREADS, 0, a>>>(bstart, bend, lg, part, buckets, ll);
     TPST_TRY(hipGetLastError());
     if (g == 0) break;
     if (red2_ok(nb))
       // lane form (fewer issue slots) for the groups with slack; the group
-      // before the last keeps the quads: its tail ends right after the last
-      // group's in a lone call
-      TPST_TRY(reduce_buckets2<F>(ar, a, buckets + b0, (size_t)(whi - wlo), nb, win + wlo, RED_PRIO, g >= 2));
+      // before the last keeps the quads in a lone call, where its tail ends
+      // right after the last group's
+      TPST_TRY(reduce_buckets2<F>(ar, a, buckets + b0, (size_t)(whi - wlo), nb, win + wlo, RED_PRIO, g >= 2 || tp));
     else
       TPST_TRY(reduce_buckets<F>(ar, a, buckets + b0, (size_t)(whi - wlo), nb, win + wlo, RED_PRIO));
     k_window_chain<F><<<1, 64, 0, a>>>(win, wlo, whi, c, nullptr, 0, contrib + g);
@@ -308,7 +374,8 @@ hipError_t msm_var(Arena& ar, hipStream_t s, const uint32_t* d_bases, const uint
   pf->begin(ST_REDUCE, t0);
   // the last group's reduction is the call's tail: the short-segment form
   // (the two-level one measured slower here: 285-290 vs 295 Mscalar/s, a lone
-  // call 5.5 vs 5.1 ms, profiles/r06/ab_g0_red2.jsonl)
+  // call 5.5 vs 5.1 ms, profiles/r06/ab_g0_red2.jsonl; and again in lane form
+  // under the next call's accumulation, 299 vs 311: profiles/fixup_order)
   TPST_TRY(reduce_buckets<F>(ar, t0, buckets, (size_t)w1, nb, win));
   pf->end(ST_REDUCE, t0);
   pf->begin(ST_COMBINE, t0);
