@@ -529,6 +529,28 @@ def test_commit_rows_partial_world_split(ctx, world):
     assert np.array_equal(orc.gt_final_exp_product(ml), T)
 
 
+@pytest.mark.parametrize("k", [0, 5, 40])
+def test_gt_final_exp_product_tree_levels(ctx, k):
+    """tpst_gt_final_exp_product past what one workgroup multiplies itself (at
+    most 4 partials): k = 5 is one tree level with a short tail chunk (8 per
+    chunk), k = 40 two levels 40 -> 5 -> 1 with a tail, k = 0 the empty
+    product.  Partials are the oracle's Miller values of single pairs; the
+    result is bit-exact against the oracle's product and final exponentiation."""
+    from testudo_amd import sqrt_pst as S
+    a, _ = orc.fr_stream(0x6F7E + k, max(k, 1))
+    b, _ = orc.fr_stream(0x6F7F + k, max(k, 1))
+    P, Q = orc.g1_mul_gen(a), orc.g2_mul_gen(b)
+    parts = np.zeros((k, 72), dtype=np.uint64)
+    for i in range(k):
+        parts[i] = orc.miller_product(P[i:i + 1], Q[i:i + 1])
+    T = S.gt_final_exp_product(ctx, parts)
+    assert np.array_equal(T, orc.gt_final_exp_product(parts))
+    if k == 0:
+        one = np.zeros(72, dtype=np.uint64)
+        one[0] = 1
+        assert np.array_equal(T, one)
+
+
 @pytest.mark.parametrize("g2", [False, True])
 def test_fixed_base_grouped_msm_vs_oracle(ctx, g2):
     """csrc/fbt.h lookup-table MSM: plain (one group), MIPP-fold groups

@@ -129,7 +129,7 @@ def test_chi_table_device(ctx):
 
 
 def test_gt_membership_and_frobenius_split_facts():
-    """The facts the verifier's GT exponentiation rests on (pairing.hip
+    """The facts the verifier's GT exponentiation rests on (pairing_wave.hip
     k_gt_pow_wave): p = x (mod r), so f^p = f^x on GT; e < r < x^4 has exact
     base-x digits; gcd(p - x, Phi12(p)) = r, so a cyclotomic f with f^p = f^x
     is in GT; and the 4-way split agrees with plain exponentiation."""

@@ -23,8 +23,6 @@ int hip_fail(tpst_ctx* ctx, hipError_t e, const char* where) {
 
 }  // namespace tpst
 
-static inline unsigned grid_for(size_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }
-
 extern "C" int tpst_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;

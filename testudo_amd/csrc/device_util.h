@@ -1,12 +1,22 @@
 // Small device/host helpers shared by the HIP translation units: typed
-// load/store of field elements and points from flat u32 buffers, error
-// plumbing for the C-ABI.
+// load/store of field elements and points from flat u32 buffers, and the
+// host's error propagation (TPST_TRY) and launch geometry (grid_for).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string>
 #include "curve.h"
 
 namespace tpst {
+
+// host: hand the first HIP error of a launch sequence to the caller
+#define TPST_TRY(x)                  \
+  do {                               \
+    hipError_t _e = (x);             \
+    if (_e != hipSuccess) return _e; \
+  } while (0)
+
+// host: workgroups of `block` threads covering n items
+static inline unsigned grid_for(size_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }
 
 // number of u32 words of a field element / affine point
 template <class F> struct Words;

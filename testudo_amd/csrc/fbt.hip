@@ -1,4 +1,5 @@
 // Fixed-base lookup tables + grouped fixed-base MSM (see fbt.h).
+#include "device_util.h"
 #include "acc_field.h"
 #include "coop.h"
 #include "fbt.h"
@@ -6,14 +7,6 @@
 #include <cstdlib>
 
 namespace tpst {
-
-#define TPST_TRY(x)                  \
-  do {                               \
-    hipError_t _e = (x);             \
-    if (_e != hipSuccess) return _e; \
-  } while (0)
-
-static inline unsigned fbt_grid(size_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }
 
 // 2^(4w) B_k for w < 64 (XYZZ): one thread per base, 252 doublings
 template <class F>
@@ -122,14 +115,14 @@ hipError_t fbt_build(Arena& ar, hipStream_t s, const uint32_t* d_bases, size_t n
   Xyzz<F>* tmp = ar.take<Xyzz<F>>(n * FBT_W);
   if constexpr (sizeof(F) == sizeof(Fq)) {  // G1 (timed: the opening's comm_list table)
     const int nw = glv ? FBT_WG : FBT_W;
-    k_fbt_pow_quad<F><<<fbt_grid(4 * n, 64), 64, 0, s>>>(d_bases, n, nw, tmp);
+    k_fbt_pow_quad<F><<<grid_for(4 * n, 64), 64, 0, s>>>(d_bases, n, nw, tmp);
     TPST_TRY(hipGetLastError());
-    k_fbt_mult8<F><<<fbt_grid(n * nw, 64), 64, 0, s>>>(tmp, n, nw, d_table);
+    k_fbt_mult8<F><<<grid_for(n * nw, 64), 64, 0, s>>>(tmp, n, nw, d_table);
   } else {  // G2 tables are built once per SRS
     if (glv) return hipErrorInvalidValue;
-    k_fbt_pow<F><<<fbt_grid(n, 64), 64, 0, s>>>(d_bases, n, tmp);
+    k_fbt_pow<F><<<grid_for(n, 64), 64, 0, s>>>(d_bases, n, tmp);
     TPST_TRY(hipGetLastError());
-    k_fbt_mult<F><<<fbt_grid(fbt_entries<F>(n), 64), 64, 0, s>>>(tmp, n, d_table);
+    k_fbt_mult<F><<<grid_for(fbt_entries<F>(n), 64), 64, 0, s>>>(tmp, n, d_table);
   }
   return hipGetLastError();
 }
@@ -323,7 +316,7 @@ hipError_t fbt_msm(Arena& ar, hipStream_t s, const uint32_t* d_table, const uint
     len = 1;
     TPST_TRY(hipMemsetAsync(a, 0, G * sizeof(Xyzz<F>), s));
   } else {
-    k_fbt_partial_quad<F><<<fbt_grid(4 * G * len, 64), 64, 0, s>>>(d_table, d_scalars, g, a);
+    k_fbt_partial_quad<F><<<grid_for(4 * G * len, 64), 64, 0, s>>>(d_table, d_scalars, g, a);
     TPST_TRY(hipGetLastError());
   }
   while (len > 1) {

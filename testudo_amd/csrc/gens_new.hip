@@ -24,8 +24,6 @@ using namespace tpst;
 
 namespace {
 
-inline unsigned grid_for(size_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
-
 // ----------------------------------------------------------- device side --
 struct SqrtConsts {
   uint32_t e[12];   // (q - 1) / 2, q = (p - 1) / 2^46

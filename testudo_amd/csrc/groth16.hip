@@ -38,15 +38,7 @@
 
 using namespace tpst;
 
-#define TPST_TRY(x)                \
-  do {                             \
-    hipError_t _e = (x);           \
-    if (_e != hipSuccess) return _e; \
-  } while (0)
-
 namespace {
-
-inline unsigned grid_for(size_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
 
 struct FrArg {  // an Fr passed by value to a kernel
   uint32_t v[8];

@@ -34,8 +34,6 @@ using namespace tpst;
 
 namespace {
 
-inline unsigned grid_for(size_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
-
 constexpr int HB_BS = 256;  // bound: columns i per block
 constexpr int HB_TJ = 64;   // bound: rows j per block (the partial-sum tile)
 

@@ -11,8 +11,6 @@
 
 using namespace tpst;
 
-static inline unsigned grid_for(size_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }
-
 // ------------------------------------------------------ microbenchmark ----
 __global__ void k_mb_fqmul(int iters, uint32_t* out) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;

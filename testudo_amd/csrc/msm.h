@@ -1,6 +1,6 @@
 // Pippenger multi-scalar multiplication engine for CDNA4 (host-side API).
 // Layout of its sources, one header per stage, no preprocessor gates:
-//   msm_common.h  TPST_TRY, grid_for, device_simds, ACC_BLOCK, REC29_WORDS
+//   msm_common.h  device_simds, ACC_BLOCK, REC29_WORDS (TPST_TRY and grid_for: device_util.h)
 //   msm_sort.h    signed digits, the scalar decomposition, the bucket sort
 //   msm_acc.h     bucket accumulation kernels and their fixups
 //   msm_reduce.h  bucket reductions (one- and two-level), the window chain
@@ -86,7 +86,7 @@ struct Arena {
     off += bytes;
     return p;
   }
-  static size_t need(size_t count, size_t elem) { return (count * elem + 255) & ~size_t(255); }
+  static constexpr size_t need(size_t count, size_t elem) { return (count * elem + 255) & ~size_t(255); }
   void release();
 };
 

@@ -1,5 +1,5 @@
-// Shared by the MSM sources (msm.h lists them): error propagation, launch
-// geometry and the constants the stages agree on.
+// Shared by the MSM sources (msm.h lists them): window counts, the device's
+// size and the constants the stages agree on.
 #pragma once
 #include <cstdlib>
 #include <string>
@@ -13,14 +13,6 @@
 #include <type_traits>
 
 namespace tpst {
-
-#define TPST_TRY(x)                          \
-  do {                                       \
-    hipError_t _e = (x);                     \
-    if (_e != hipSuccess) return _e;         \
-  } while (0)
-
-static inline unsigned grid_for(size_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }
 
 static inline int bit_length(uint64_t v) {
   int b = 0;

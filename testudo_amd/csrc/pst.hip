@@ -6,8 +6,6 @@
 
 namespace tpst {
 
-static inline unsigned grid_for(size_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }
-
 __global__ void k_fr_conv(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, size_t n, int to_mont_flag) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;

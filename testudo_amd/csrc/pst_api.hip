@@ -739,7 +739,7 @@ static int final_exp_product(tpst_ctx* ctx, const uint64_t* partials, const void
     TPST_HIP(ctx, points_to_mont<Fq>(s, up.u(), up.u(), 6 * k));  // 12 Fq = 6 "points"
   }
   ctx->arena.reset();
-  TPST_HIP(ctx, ctx->arena.reserve(multi_pairing_scratch(1, k)));
+  TPST_HIP(ctx, ctx->arena.reserve(gt_product_scratch(1, k)));
   TPST_HIP(ctx, gt_product_final(ctx->arena, s, (const Fq12*)up.p, 1, k, (Fq12*)out.p));
   TPST_HIP(ctx, fq12_from_mont(s, (Fq12*)out.p, out.u() + sizeof(Fq12) / 4, 1));
   TPST_HIP(ctx, hipMemcpyAsync(T, out.u() + sizeof(Fq12) / 4, 576, hipMemcpyDeviceToHost, s));
@@ -926,7 +926,7 @@ int tpst::srs_fbt(tpst_ctx* ctx, SrsState* st, int odd) {
 // exponentiations: the chains run on host threads (host_curve.h, ~30 ns per
 // Fq product against ~1.6 us on a lone GPU lane), the pairing products in ONE
 // device launch (groups padded with infinity pairs), the GT powers on a side
-// stream (pairing.hip k_gt_pow_wave).
+// stream (pairing_wave.hip k_gt_pow_wave).
 static bool gt_is_one(const uint64_t* gt) {
   if (gt[0] != 1) return false;
   for (int i = 1; i < 72; i++)

@@ -117,7 +117,7 @@ int open_streams(tpst_ctx* ctx, size_t n_events, size_t pinned_bytes, bool comm)
 //     120) bilinearity splits round r's cross products into eight pairing
 //     products of round r-1's vectors that do not involve c = c_{r-1},
 //       t_l = A0 A3 A1^(c^-1) A2^c,  t_r = B0 B3 B1^(c^-1) B2^c
-//     (pairing.hip, mipp_lookahead), so once c is known the critical path is
+//     (pairing.hip mipp_lookahead, pairing_mipp.hip the combination), so once c is known the critical path is
 //     four GT exponentiations (base-x Frobenius splitting, ~0.7 ms) and two
 //     products instead of fold + Miller loops + final exponentiations
 //     (~3.3 ms); comms_t -> host.
@@ -941,6 +941,11 @@ int Opening::enqueue_lookahead(const Round& q) {
       g.set_stride = Ca;
     }
     TPST_HIP(ctx, fbt_msm<Fq>(arD, sD, tA, sc, g, (Xyzz<Fq>*)b.xl[r & 1].p));
+    // fbt_msm resets arD and takes its own two buffers; its result is in
+    // b.xl and the look-ahead follows it on sD, so they are dead by then and
+    // the look-ahead takes from the start again: arD holds the larger of the
+    // two needs (fbt_msm reserves its own), not their sum
+    arD.reset();
     const int src = la_src(r);  // h^(0), or h^(src) prepared by stream C in round src
     const uint32_t* hp = loc ? H0l : H0;
     const LineCoeff* lp = loc ? L0l : L0;

@@ -84,7 +84,7 @@ inline void xyzz_to_canonical_host(const uint8_t* raw, size_t n, uint64_t* out) 
 }
 
 // base-x digits of a canonical Fr e (e < r < x^4): e = sum_j out[j] x^j, for
-// the GT exponentiations by Frobenius splitting (pairing.hip k_gt_pow_wave)
+// the GT exponentiations by Frobenius splitting (pairing_wave.hip k_gt_pow_wave)
 inline void base_x_digits(const uint64_t* e, uint64_t* out) {
   uint64_t q[4] = {e[0], e[1], e[2], e[3]};
   for (int t = 0; t < 4; t++) {

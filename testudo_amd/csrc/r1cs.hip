@@ -29,15 +29,7 @@
 
 using namespace tpst;
 
-#define TPST_TRY_HIP(x)                \
-  do {                                 \
-    hipError_t _e = (x);               \
-    if (_e != hipSuccess) return _e;   \
-  } while (0)
-
 namespace {
-
-inline unsigned grid_for(size_t n, unsigned b) { return (unsigned)((n + b - 1) / b); }
 
 // ------------------------------------------------------------ kernels ----
 // out[i] = prod_j (bit (ell-1-j) of i ? r_j : 1 - r_j)   (MSB-first, r Montgomery)
@@ -443,20 +435,20 @@ Fr uni_eval(const Fr* cs, int n, const Fr& r) {
 // CSR (by key = rows) or CSC (by key = cols) of one matrix from device triples
 static hipError_t build_compressed(hipStream_t s, const uint32_t* key, const uint32_t* other, const uint32_t* val,
                                    size_t nnz, size_t nkeys, DevBuf& ptr, DevBuf& idx, DevBuf& vout) {
-  TPST_TRY_HIP(ptr.alloc((nkeys + 1) * 4));
-  TPST_TRY_HIP(idx.alloc(nnz ? nnz * 4 : 4));
-  TPST_TRY_HIP(vout.alloc(nnz ? nnz * 32 : 32));
+  TPST_TRY(ptr.alloc((nkeys + 1) * 4));
+  TPST_TRY(idx.alloc(nnz ? nnz * 4 : 4));
+  TPST_TRY(vout.alloc(nnz ? nnz * 32 : 32));
   DevBuf cnt, cursor, tmp;
-  TPST_TRY_HIP(cnt.alloc((nkeys + 1) * 4));
-  TPST_TRY_HIP(cursor.alloc((nkeys + 1) * 4));
-  TPST_TRY_HIP(hipMemsetAsync(cnt.p, 0, (nkeys + 1) * 4, s));
+  TPST_TRY(cnt.alloc((nkeys + 1) * 4));
+  TPST_TRY(cursor.alloc((nkeys + 1) * 4));
+  TPST_TRY(hipMemsetAsync(cnt.p, 0, (nkeys + 1) * 4, s));
   if (nnz) k_count<<<grid_for(nnz, 256), 256, 0, s>>>(key, nnz, cnt.u());
-  TPST_TRY_HIP(hipGetLastError());
-  TPST_TRY_HIP(tmp.alloc(scan_sort::scan_scratch(nkeys + 1) * 4 + 4));
-  TPST_TRY_HIP(scan_sort::scan_excl_u32(s, cnt.u(), ptr.u(), nkeys + 1, tmp.u()));
-  TPST_TRY_HIP(hipMemcpyAsync(cursor.p, ptr.p, (nkeys + 1) * 4, hipMemcpyDeviceToDevice, s));
+  TPST_TRY(hipGetLastError());
+  TPST_TRY(tmp.alloc(scan_sort::scan_scratch(nkeys + 1) * 4 + 4));
+  TPST_TRY(scan_sort::scan_excl_u32(s, cnt.u(), ptr.u(), nkeys + 1, tmp.u()));
+  TPST_TRY(hipMemcpyAsync(cursor.p, ptr.p, (nkeys + 1) * 4, hipMemcpyDeviceToDevice, s));
   if (nnz) k_scatter<<<grid_for(nnz, 256), 256, 0, s>>>(key, other, val, nnz, cursor.u(), idx.u(), vout.u());
-  TPST_TRY_HIP(hipGetLastError());
+  TPST_TRY(hipGetLastError());
   return hipStreamSynchronize(s);  // the scratch buffers are freed on return
 }
 

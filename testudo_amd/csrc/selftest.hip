@@ -20,8 +20,6 @@
 using namespace tpst;
 namespace st = tpst::selftest;
 
-static inline unsigned grid_for(size_t n, unsigned block) { return (unsigned)((n + block - 1) / block); }
-
 template <int FAM>
 __global__ void __launch_bounds__(64) k_selftest_field(int idx, size_t n, const uint32_t* __restrict__ a,
                                                        const uint32_t* __restrict__ b, uint32_t* __restrict__ out) {
