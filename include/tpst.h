@@ -520,6 +520,63 @@ int tpst_hyrax_eval_verify_plain(tpst_ctx* ctx, const tpst_gens* gens, const uin
 /* DensePolynomial::evaluate (dense_mlpoly.rs:408-414) on the device */
 int tpst_dense_evaluate(tpst_ctx* ctx, const uint64_t* Z, int ell, const uint64_t* r, uint64_t* out_fr);
 
+/* ---- SPARK grand products (csrc/product_tree.hip) ---------------------------
+ * ProductCircuitEvalProofBatched::{prove, verify} (product_tree.rs:255-476)
+ * over SumcheckInstanceProof::prove_cubic_batched (sumcheck.rs:220-385) and
+ * PoseidonTranscript<Fr>: the memory-checking argument ProductLayerProof::prove
+ * (sparse_mlpoly.rs:1053-1236) runs twice per R1CSEvalProof.
+ *
+ * P product circuits over 2^ell entries each (ProductCircuit::new, 1 <= ell <=
+ * 30, P >= 1) and D dot-product circuits (DotProductCircuit, already split:
+ * D is 0 or even, circuits 2k and 2k + 1 the halves of one unsplit triple) of
+ * 2^(ell - 1) entries each; P + D <= TPST_PRODCIRCUIT_MAX_INSTANCES.
+ *
+ * The proof is one caller-owned flat buffer of tpst_prodcircuit_proof_len(ell,
+ * P, D) canonical Fr (4 u64 each), in this order:
+ *   1. the layer proofs in the reference's push order (from the top layer
+ *      down): layer proof i, i = 0 .. ell - 1, has i rounds of 4 coefficients,
+ *      constant first -- ell (ell - 1) / 2 round polynomials in all;
+ *   2. ell x P claims_prod_left (layer proof i, then instance), then ell x P
+ *      claims_prod_right;
+ *   3. the 3 x D final dot-product claims: D left, D right, D weight.
+ * `tr` is updated in place. */
+#define TPST_PRODCIRCUIT_MAX_INSTANCES 4096
+/* Fr count of the flat proof = 2 ell (ell - 1) + 2 ell P + 3 D; 0 for
+ * dimensions the calls below reject */
+size_t tpst_prodcircuit_proof_len(int ell, size_t P, size_t D);
+/* prove: polys = P x 2^ell canonical Fr, dotp_left / dotp_right / dotp_weight =
+ * D x 2^(ell - 1) each (NULL with claims_dotp when D == 0).  Returns
+ * claims_prod = every circuit's ProductCircuit::evaluate (P Fr), claims_dotp =
+ * every DotProductCircuit::evaluate (D Fr) and rand (ell Fr).  The inputs are
+ * not modified: the layers are built in a library-owned device arena.
+ * _dev: the four inputs are device buffers on the context's device, ordered
+ * after the work queued on tpst_stream; their values must be canonical (not
+ * checked, as for tpst_hyrax_eval_prove_dev).
+ * TPST_E_ARG: a null argument, a value >= r, ell or P out of range, odd D, a
+ * transcript state no sponge can be in.  TPST_E_HIP: a HIP runtime failure
+ * (the arena needs about 32 (2 P + 1.5 D + 1) 2^ell bytes). */
+int tpst_prodcircuit_prove(tpst_ctx* ctx, int ell, size_t P, const uint64_t* polys, size_t D,
+                           const uint64_t* dotp_left, const uint64_t* dotp_right, const uint64_t* dotp_weight,
+                           tpst_transcript_fr* tr, uint64_t* proof, uint64_t* claims_prod, uint64_t* claims_dotp,
+                           uint64_t* rand);
+int tpst_prodcircuit_prove_dev(tpst_ctx* ctx, int ell, size_t P, const void* d_polys, size_t D,
+                               const void* d_dotp_left, const void* d_dotp_right, const void* d_dotp_weight,
+                               tpst_transcript_fr* tr, uint64_t* proof, uint64_t* claims_prod, uint64_t* claims_dotp,
+                               uint64_t* rand);
+/* verify (product_tree.rs:379-476 with SumcheckInstanceProof::verify,
+ * sumcheck.rs:29-63): host only, no context.  Returns claims_out = the P
+ * product claims at rand, claims_dotp_out = 3 D / 2 Fr, (left, right, weight)
+ * of every unsplit dot-product triple at rand, and rand (ell Fr); the caller
+ * checks those against its polynomials.
+ * TPST_OK: every round and layer check holds.  TPST_E_VERIFY: a failed round
+ * check (G(0) + G(1) = e), a failed layer equation, or a non-canonical Fr in
+ * the proof or the claims (checked before the transcript absorbs anything; on
+ * any failure `tr` and the outputs are left untouched).  TPST_E_ARG: a null
+ * argument or dimensions as above. */
+int tpst_prodcircuit_verify(int ell, size_t P, size_t D, const uint64_t* claims_prod, const uint64_t* claims_dotp,
+                            const uint64_t* proof, tpst_transcript_fr* tr, uint64_t* claims_out,
+                            uint64_t* claims_dotp_out, uint64_t* rand);
+
 /* ---- Groth16 over BLS12-377 (csrc/groth16.hip) ----
  * The prover behind R1CSProof::prove_verifier (r1csproof.rs:374-434,
  * Groth16::<E>::prove at :421): ark-groth16 create_proof with the
@@ -614,7 +671,10 @@ int tpst_selftest_curve(tpst_ctx* ctx, int op, size_t n, const uint64_t* p, cons
  * dominant kernel), 4 bucket reduction, 5 window combine, 6 K1 row sort;
  * 15 / 16: tpst_r1cs_evaluate's eq tables / its reduction and partial sum;
  * 17 / 18 / 19: tpst_hyrax_eval_prove's eq tables / bound / dot-product proof
- * (first launch to last result, the host work between launches included). */
+ * (first launch to last result, the host work between launches included);
+ * 20 / 21: tpst_prodcircuit_prove's layer build / all layer proofs (host work
+ * between launches included); 22 / 23: round 0 / round 1 of its layer 0 alone
+ * (round kernel and reduce). */
 int tpst_profile_enable(tpst_ctx* ctx, int on);
 int tpst_profile_reset(tpst_ctx* ctx);
 int tpst_profile_read(tpst_ctx* ctx, int stage, double* total_ms, uint64_t* launches);

@@ -8,3 +8,4 @@ verify``, sqrt_pst.rs:14-265).
 from .engine import Context, Gens, TpstError  # noqa: F401
 from .hyrax import (DotProductProof, FrTranscript, HyraxGens, dense_evaluate, dotprod_prove,  # noqa: F401
                     dotprod_verify, eval_prove, eval_verify, eval_verify_plain)
+from . import product_tree  # noqa: F401,E402

@@ -123,6 +123,12 @@ PROTOTYPES = [
     ("tpst_hyrax_eval_verify", C.c_int, [_vp, _vp, _u64p, C.c_int, _u64p, _u64p, _u64p, _vp, _vp]),
     ("tpst_hyrax_eval_verify_plain", C.c_int, [_vp, _vp, _u64p, C.c_int, _u64p, _u64p, _u64p, _vp, _vp]),
     ("tpst_dense_evaluate", C.c_int, [_vp, _u64p, C.c_int, _u64p, _u64p]),
+    ("tpst_prodcircuit_proof_len", _sz, [C.c_int, _sz, _sz]),
+    ("tpst_prodcircuit_prove", C.c_int, [_vp, C.c_int, _sz, _u64p, _sz, _u64p, _u64p, _u64p, _vp, _u64p, _u64p,
+                                         _u64p, _u64p]),
+    ("tpst_prodcircuit_prove_dev", C.c_int, [_vp, C.c_int, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _u64p, _u64p, _u64p,
+                                             _u64p]),
+    ("tpst_prodcircuit_verify", C.c_int, [C.c_int, _sz, _sz, _u64p, _u64p, _u64p, _vp, _u64p, _u64p, _u64p]),
     ("tpst_groth16_setup", C.c_int, [_vp, _vp, _u64p, C.POINTER(_vp)]),
     ("tpst_groth16_pk_free", None, [_vp]),
     ("tpst_groth16_domain", C.c_int, [_vp, C.POINTER(_sz)]),

@@ -45,6 +45,10 @@ enum MsmStage {
   // tpst_hyrax_eval_prove: the L / R eq tables; bound (partials and their sum); the dot-product proof from its
   // first launch to the last round's results (the host's transcript and point work between launches included)
   ST_HYRAX_EQ, ST_HYRAX_BOUND, ST_HYRAX_ROUNDS,
+  // tpst_prodcircuit_prove: the layer build (Montgomery copies, one pass per layer, the dot products'
+  // evaluations); every layer proof from the first squeeze to the last claims (the host's transcript between
+  // launches included); round 0 / round 1 of layer 0 alone (round kernel + reduce: the bandwidth-bound rounds)
+  ST_PRODTREE_BUILD, ST_PRODTREE_ROUNDS, ST_PRODTREE_ROUND0, ST_PRODTREE_ROUND1,
   N_STAGES
 };
 

@@ -401,6 +401,10 @@ Fr fr_small(uint32_t v) {
   return to_mont(a);
 }
 
+}  // namespace
+
+namespace tpst {
+
 // UniPoly::from_evals (unipoly.rs:15-45), Montgomery in/out
 void from_evals(const Fr* e, int n, Fr* cs) {
   static const Fr i2 = inv(fr_small(2)), i6 = inv(fr_small(6));
@@ -430,7 +434,25 @@ Fr uni_eval(const Fr* cs, int n, const Fr& r) {
   return out;
 }
 
-}  // namespace
+// EqPolynomial::evals (dense_mlpoly.rs:231-250) of ell Montgomery coordinates
+// on the device, MSB-first: short tables straight from k_eq_evals, longer ones
+// as the outer product of the tables of the point's halves (d_half: scratch of
+// eq_table_scratch(ell) Fr)
+hipError_t eq_table(hipStream_t s, const uint32_t* d_r, int ell, uint32_t* d_half, uint32_t* d_out) {
+  const size_t n = (size_t)1 << ell;
+  if (ell < EQ_SPLIT_MIN) {
+    k_eq_evals<<<grid_for(n, 256), 256, 0, s>>>(d_r, ell, n, d_out);
+    return hipGetLastError();
+  }
+  const int lo = ell / 2, hi = ell - lo;
+  uint32_t* d_lo = d_half + 8 * ((size_t)1 << hi);
+  k_eq_evals<<<grid_for((size_t)1 << hi, 256), 256, 0, s>>>(d_r, hi, (size_t)1 << hi, d_half);
+  k_eq_evals<<<grid_for((size_t)1 << lo, 256), 256, 0, s>>>(d_r + 8 * (size_t)hi, lo, (size_t)1 << lo, d_lo);
+  k_eq_outer<<<grid_for(n, 256), 256, 0, s>>>(d_half, d_lo, lo, n, d_out);
+  return hipGetLastError();
+}
+
+}  // namespace tpst
 
 // CSR (by key = rows) or CSC (by key = cols) of one matrix from device triples
 static hipError_t build_compressed(hipStream_t s, const uint32_t* key, const uint32_t* other, const uint32_t* val,

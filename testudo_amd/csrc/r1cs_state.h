@@ -15,6 +15,21 @@ inline int log2_exact(size_t n) {
   return ((size_t)1 << l) == n ? l : -1;
 }
 
+// ---------------------------- r1cs.hip, for the batched sum-checks of
+// product_tree.hip
+// UniPoly::from_evals (unipoly.rs:15-45): n = 3 or 4 evaluations at 0..n-1 ->
+// coefficients, constant first; UniPoly::evaluate (:66-74).  Host, Montgomery.
+void from_evals(const Fr* e, int n, Fr* cs);
+Fr uni_eval(const Fr* cs, int n, const Fr& r);
+// EqPolynomial::evals of ell Montgomery coordinates at d_r (MSB-first) into
+// d_out (2^ell Fr, 32-byte aligned) by the k_eq_evals / k_eq_outer path;
+// d_half: eq_table_scratch(ell) Fr of scratch
+constexpr int EQ_SPLIT_MIN = 10;  // below: one k_eq_evals launch, ell products per entry
+inline size_t eq_table_scratch(int ell) {
+  return ell < EQ_SPLIT_MIN ? 0 : ((size_t)1 << (ell - ell / 2)) + ((size_t)1 << (ell / 2));
+}
+hipError_t eq_table(hipStream_t s, const uint32_t* d_r, int ell, uint32_t* d_half, uint32_t* d_out);
+
 }  // namespace tpst
 
 // ================================================================ state ==

@@ -113,7 +113,8 @@ class Context:
               # tpst_r1cs_evaluate: the two eq tables; the reduction kernel and its partial sum
               "r1cs_eval_eq", "r1cs_eval",
               # tpst_hyrax_eval_prove: the L / R eq tables; bound; the dot-product proof (host work included)
-              "hyrax_eq", "hyrax_bound", "hyrax_rounds")
+              "hyrax_eq", "hyrax_bound", "hyrax_rounds",
+              "prodtree_build", "prodtree_rounds", "prodtree_round0", "prodtree_round1")
 
     def profile(self, on: bool):
         self.check(self.lib.tpst_profile_enable(self.h, 1 if on else 0), "tpst_profile_enable")

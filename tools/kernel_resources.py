@@ -55,6 +55,12 @@ HOT = [
     "k_bound_sum",
     "k_cross",
     "k_fold_rows",
+    # the grand-product argument (product_tree.hip): layer build, batched round, reduce
+    "k_pt_layer",
+    "k_pt_dotp",
+    "k_pt_round",
+    "k_pt_reduce",
+    "k_pt_finals",
 ]
 
 FIELDS = {
