@@ -665,6 +665,41 @@ int tpst_selftest_inv(tpst_ctx* ctx, size_t n, const uint64_t* in, uint64_t* out
  * op, a null pointer or n == 0 is TPST_E_ARG (q may be null for glv_split). */
 int tpst_selftest_field(tpst_ctx* ctx, int op, size_t n, const uint64_t* a, const uint64_t* b, uint64_t* out);
 int tpst_selftest_curve(tpst_ctx* ctx, int op, size_t n, const uint64_t* p, const uint64_t* q, uint64_t* out);
+/* Self-test of the pairing's two Fq12 engines on n caller-chosen operands: the
+ * RNS chain engine (csrc/rns_engine.h, engine 0) and the radix wave engine
+ * (csrc/wave_tower.h, engine 1), run through the engines' own loads, stages
+ * and stores.  op = engine << 8 | in codec << 7 | out codec << 6 | index
+ * (csrc/selftest_ops.h: tower_op / tower_op_valid / tower_a_words /
+ * tower_b_words / tower_out_words).
+ *   codec 0 (FQ): an Fq12 as 12 field.h Montgomery Fq in tower order, 144 u32
+ *     words per element; results canonical (< p).
+ *   codec 1 (RES, RNS engine only): the engine's 12 x 32 raw residue words
+ *     (word 32 k + c = channel c of coefficient k; channels 0..14 base B, 15
+ *     mod 2^32, 16..30 base B', 31 idle: ignored going in, unspecified coming
+ *     out): any integer < 16 p per coefficient going in, the stage's
+ *     bit-exact residues coming out.
+ *   index 0 F12_MUL (a b), 1 F12_SQR, 2 CYC_SQR (the Granger-Scott formula, a
+ *     polynomial identity on any a), 3 / 4 / 5 FROB1 / FROB2 / FROB3, 6 CONJ,
+ *     7 COPY (under FQ -> FQ the load / store round trip): single stages;
+ *   8 INV: the inversion both final exponentiations start with (rc_inv /
+ *     fe_inv).  a = 0 gives 0 (the tower norm is 0 and the device Fq inverses
+ *     map 0 to 0, tpst_selftest_inv), where arkworks' Field::inverse returns
+ *     None: callers that can meet 0 test for it first.  A final
+ *     exponentiation of 0 is therefore 0 on both engines; no entry point of
+ *     this library feeds it one from valid inputs.
+ *   9 FINAL_EXP (RNS, FQ only): the final exponentiation of a alone.
+ *   10 G2_PREPARE (RNS, FQ only): a = n affine G2 points (Montgomery x, y: 48
+ *     words each) -> 69 line coefficients (c0, c1, c2: 72 words) per point,
+ *     coefficient-major: coefficient j of point i at out + 72 (j n + i) words.
+ *   11 GT_POW (wave only): a = base, b = 4 u64 base-x exponent digits (8
+ *     words) -> n x 144 result words, then n words ok[i] (1: base[i] is in
+ *     GT), then one zero word if n is odd; the result of a non-member is 0.
+ *   12 PASS (RNS only): no stage, the load straight into the store: FQ -> RES
+ *     is the engine's load alone, RES -> FQ its store alone on a's integers.
+ * The wave engine runs F12_MUL, CYC_SQR, FROB1, FROB2, CONJ, INV and GT_POW.
+ * b is read by F12_MUL and GT_POW only and may be null otherwise.  A bad op, a
+ * null pointer, n == 0 or n > 2^16 is TPST_E_ARG. */
+int tpst_selftest_tower(tpst_ctx* ctx, int op, size_t n, const uint64_t* a, const uint64_t* b, uint64_t* out);
 
 /* Per-stage HIP-event timing of the MSM pipeline on the context's stream.
  * stage: 0 decompose, 1 sort, 2 bucket bounds, 3 bucket accumulation (the

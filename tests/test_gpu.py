@@ -551,6 +551,56 @@ def test_gt_final_exp_product_tree_levels(ctx, k):
         assert np.array_equal(T, one)
 
 
+def _edge_partials():
+    """non-zero Fq12 partials from tests/tower_vectors.py's classes a (coefficient
+    edges), c (a, a^-1 and -a^-1: products of exactly 1 and -1) and f (1, -1,
+    elements of Fq and Fq2, c1 = 0, c0 = 0, pure w, norm 1 and p-1), canonical words"""
+    import tower_vectors as V
+    vs = [(n, v) for n, v in V.final_exp_vectors() if any(v)]
+    by = dict(V.structured())
+    for nm in ("f.rnd", "f.norm p-1", "f.pure w"):
+        a = by[nm]
+        ai = V.ref("inv", a)
+        vs += [("c.a " + nm, a), ("c.a^-1 " + nm, ai), ("c.a again " + nm, a),
+               ("c.-a^-1 " + nm, [(O.P - x) % O.P for x in ai])]
+    assert {"f.one", "f.minus one", "f.Fq 2", "f.pure w"} <= {n for n, _ in vs}
+    return [n for n, _ in vs], np.stack([V.words(v, 12).view(np.uint64).reshape(72) for _, v in vs])
+
+
+@pytest.mark.parametrize("k", [1, 5])
+def test_gt_final_exp_product_edge_partials(ctx, k):
+    """tpst_gt_final_exp_product (the wave engine's final exponentiation) on
+    edge partials, k = 1 each alone and k = 5 in overlapping runs of five,
+    against the oracle; zero is not a partial the header defines"""
+    from testudo_amd import sqrt_pst as S
+    names, parts = _edge_partials()
+    for i in range(0, len(parts) - k + 1, 1 if k == 1 else 2):
+        T = S.gt_final_exp_product(ctx, parts[i:i + k])
+        assert np.array_equal(T, orc.gt_final_exp_product(parts[i:i + k])), names[i:i + k]
+
+
+def test_multi_pairing_of_infinities_is_one(ctx):
+    one = np.zeros(72, dtype=np.uint64)
+    one[0] = 1
+    for n in (1, 2, 5):
+        g1 = np.zeros((n, 12), dtype=np.uint64)
+        g2 = np.zeros((n, 24), dtype=np.uint64)
+        assert np.array_equal(ctx.multi_pairing(g1, g2), one), n
+
+
+def test_multi_pairing_of_a_point_and_its_negative_is_one(ctx):
+    """e(P, Q) e(-P, Q) = 1 exactly, as the oracle has it"""
+    Pt = orc.g1_mul_gen(fr_array([0x1234567]))
+    Q = orc.g2_mul_gen(fr_array([0x89ABCDE]))
+    x, y = g1_from_array(Pt[0])[0]
+    assert O.g1_add((x, y), (x, O.P - y)) is None
+    g1 = np.concatenate([Pt, g1_array([(x, O.P - y)])])
+    g2 = np.concatenate([Q, Q])
+    out = ctx.multi_pairing(g1, g2)
+    assert out[0] == 1 and not out[1:].any()
+    assert np.array_equal(out, orc.multi_pairing(g1, g2))
+
+
 @pytest.mark.parametrize("g2", [False, True])
 def test_fixed_base_grouped_msm_vs_oracle(ctx, g2):
     """csrc/fbt.h lookup-table MSM: plain (one group), MIPP-fold groups

@@ -1,6 +1,6 @@
 // RNS-engine device pieces shared by the pairing units (pairing_kernels.h
-// lists them): the workgroup shape of the Fq12 kernels, the final
-// exponentiation and the short product chain.
+// lists them): the workgroup shape of the Fq12 kernels, the Fq12 inversion,
+// the final exponentiation and the short product chain.
 //
 // An Fq12 kernel on the RNS engine (rns_engine.h) runs two values per
 // workgroup (the two halves of every wave) on twelve waves, one per Fq12
@@ -37,15 +37,12 @@ __device__ __forceinline__ int rc_exp_by_x(const rns::Eng& e, const rns::Lane& L
   return cur;
 }
 
-// f (register F) -> f^(3(p^12-1)/r); returns the result register.  Same chain
-// as final_exponentiation() in pairing.h (eprint 2020/875).  regs: ten Fq12
-// registers, I: 24 slots of inversion temporaries, sh_n: the two chains'
-// Fq-norms handed to the inverting waves and back.  Contains __syncthreads.
-// Inlined into exactly two kernels, k_chain_final_rns and k_prod_final_rns
-// (pairing.hip says what a third cost).
-__device__ __forceinline__ int rc_final_exp(const rns::Eng& e, const rns::Lane& L, int F, int regs, int I, Fq* sh_n) {
+// f (register F) -> f^-1 in the twelve slots from D, through the tower norms
+// and one Fq inversion (field.h inv(Fq12)).  I: 24 slots of temporaries, sh_n:
+// the two chains' Fq-norms handed to the inverting waves and back.  f = 0
+// gives 0: the norm is 0 and inv_w(0) = 0.  Contains __syncthreads.
+__device__ __forceinline__ void rc_inv(const rns::Eng& e, const rns::Lane& L, int F, int I, int D, Fq* sh_n) {
   using namespace rns;
-#define R(i) (regs + 12 * (i))
   stage<OP_INV1>(e, L, F, 0, I + 0);         // t = c0^2 - v c1^2
   stage<OP_INV2>(e, L, I + 0, 0, I + 6);     // Fq6 adjugate c'
   stage<OP_INV3>(e, L, I + 6, I + 0, I + 12);  // Fq6 norm t'
@@ -60,7 +57,18 @@ __device__ __forceinline__ int rc_final_exp(const rns::Eng& e, const rns::Lane& 
   load(e, L, sh_n, sh_n + 1, I + 15, 1);
   stage<OP_INV5>(e, L, I + 12, I + 15, I + 16);  // t'^-1
   stage<OP_INV6>(e, L, I + 6, I + 16, I + 18);   // t^-1
-  stage<OP_INV7>(e, L, F, I + 18, R(0));         // f^-1
+  stage<OP_INV7>(e, L, F, I + 18, D);            // f^-1
+}
+
+// f (register F) -> f^(3(p^12-1)/r); returns the result register.  Same chain
+// as final_exponentiation() in pairing.h (eprint 2020/875).  regs: ten Fq12
+// registers, I and sh_n: rc_inv's.  Contains __syncthreads.
+// Inlined into exactly two kernels, k_chain_final_rns and k_prod_final_rns
+// (pairing.hip says what a third cost).
+__device__ __forceinline__ int rc_final_exp(const rns::Eng& e, const rns::Lane& L, int F, int regs, int I, Fq* sh_n) {
+  using namespace rns;
+#define R(i) (regs + 12 * (i))
+  rc_inv(e, L, F, I, R(0), sh_n);
   // easy part
   stage<OP_CONJ>(e, L, F, 0, R(1));
   stage<OP_F12_MUL>(e, L, R(1), R(0), R(2));  // r = conj(f) f^-1

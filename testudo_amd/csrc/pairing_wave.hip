@@ -6,7 +6,7 @@
 //   gt_pow_wave       the verifier's GT membership tests and exponentiations
 #include "device_util.h"
 #include "pairing_kernels.h"
-#include "wave_tower.h"
+#include "pairing_wave_fe.h"
 
 namespace tpst {
 
@@ -14,21 +14,9 @@ namespace tpst {
 constexpr int FW = (int)plan::FW;          // waves per workgroup
 constexpr int FW_SLOTS = 64 + 36;          // PROD, ACC, IN, TMP per wave
 constexpr int FE_SLOTS = 10 * 12 + 24;     // wave 0: 10 registers + inversion temporaries
-// the op programs of k_final_wave and k_gt_pow_wave, addressed by the enum below
-constexpr int FE_OPS[] = {wave::OP_F12_MUL, wave::OP_CYC_SQR, wave::OP_FROB1, wave::OP_FROB2,
-                          wave::OP_CONJ,    wave::OP_INV1,    wave::OP_INV2,  wave::OP_INV3,
-                          wave::OP_INV4,    wave::OP_INV5,    wave::OP_INV6,  wave::OP_INV7};
-constexpr int N_FE_OPS = sizeof(FE_OPS) / sizeof(FE_OPS[0]);
-constexpr wave::OpSet<N_FE_OPS> FE_SET(FE_OPS);
-constexpr int FW_PROG = FE_SET.words;
+// (the op programs FE_SET of k_final_wave and k_gt_pow_wave: pairing_wave_fe.h)
 constexpr size_t FW_LDS = (size_t)(FW_PROG + (wave::N_CONSTS + FW * FW_SLOTS + FE_SLOTS) * wave::SLOT) * 4;
 static_assert(FW_LDS <= 65536, "final-exponentiation kernel LDS");
-
-enum { FE_MUL, FE_CYC, FE_FROB1, FE_FROB2, FE_CONJ, FE_INV1 };  // FE_INV1 + k: OP_INV(1 + k), k < 7
-static_assert(FE_OPS[FE_MUL] == wave::OP_F12_MUL && FE_OPS[FE_CONJ] == wave::OP_CONJ &&
-                  FE_OPS[FE_INV1] == wave::OP_INV1 && FE_OPS[FE_INV1 + 6] == wave::OP_INV7 &&
-                  FE_INV1 + 7 == N_FE_OPS,
-              "FE_* index FE_OPS");
 
 __device__ int fe_exp_by_x(const wave::Eng& e, const wave::lds_t* prog, int src, int r1, int r2) {
   int cur = src;
@@ -47,20 +35,10 @@ __device__ int fe_exp_by_x(const wave::Eng& e, const wave::lds_t* prog, int src,
 
 // f (register F) -> f^(3(p^12-1)/r); returns the result register.  Same chain
 // as final_exponentiation() in pairing.h (eprint 2020/875).  regs: ten Fq12
-// registers, I: 24 slots of inversion temporaries; N(f) is inverted on lane 0.
+// registers, I: 24 slots of inversion temporaries (fe_inv).
 __device__ int fe_final_exp(const wave::Eng& e, const wave::lds_t* prog, int F, int regs, int I) {
-  const int lane = threadIdx.x & 63;
 #define R(i) (regs + 12 * (i))
-  // f^-1 through the tower norms and one Fq inversion
-  wave::run(e, prog + FE_SET.off[FE_INV1 + 0], F, 0, I + 0);        // t = c0^2 - v c1^2
-  wave::run(e, prog + FE_SET.off[FE_INV1 + 1], I + 0, 0, I + 6);    // Fq6 adjugate c'
-  wave::run(e, prog + FE_SET.off[FE_INV1 + 2], I + 6, I + 0, I + 12);  // Fq6 norm t'
-  wave::run(e, prog + FE_SET.off[FE_INV1 + 3], I + 12, 0, I + 14);  // Fq2 norm n
-  if (lane == 0) wave::put_slot(e.lds, I + 15, inv(wave::get_slot(e.lds, I + 14)));
-  wave::wave_sync();
-  wave::run(e, prog + FE_SET.off[FE_INV1 + 4], I + 12, I + 15, I + 16);  // t'^-1
-  wave::run(e, prog + FE_SET.off[FE_INV1 + 5], I + 6, I + 16, I + 18);   // t^-1
-  wave::run(e, prog + FE_SET.off[FE_INV1 + 6], F, I + 18, R(0));         // f^-1
+  fe_inv(e, prog, F, I, R(0));  // f^-1 through the tower norms and one Fq inversion
   // easy part
   wave::run(e, prog + FE_SET.off[FE_CONJ], F, 0, R(1));
   wave::run(e, prog + FE_SET.off[FE_MUL], R(1), R(0), R(2));  // r = conj(f) f^-1

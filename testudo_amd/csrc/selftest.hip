@@ -1,6 +1,7 @@
 // Self-tests of the device arithmetic below the kernels (tpst_selftest_field /
 // tpst_selftest_curve): element-wise runs of the building blocks
-// (selftest_ops.h) on caller-chosen operands.  64-thread blocks, every lane
+// (selftest_ops.h) on caller-chosen operands; and of the pairing's two Fq12
+// engines (tpst_selftest_tower, at the end).  64-thread blocks, every lane
 // active: the threads past the last element recompute it and store nothing,
 // which keeps the quads of coop.h and the pairs of pair_fq2.h whole.
 //
@@ -15,6 +16,9 @@
 #include "coop.h"
 #include "pair_fq2.h"
 #include "glv.h"
+#include "pairing_kernels.h"
+#include "pairing_rns_chain.h"
+#include "pairing_wave_fe.h"
 #include "selftest_ops.h"
 
 using namespace tpst;
@@ -227,5 +231,154 @@ extern "C" int tpst_selftest_curve(tpst_ctx* ctx, int op, size_t n, const uint64
   TPST_HIP(ctx, hipGetLastError());
   TPST_HIP(ctx, hipMemcpyAsync(out, d_o, n * w * 4, hipMemcpyDeviceToHost, ctx->stream));
   TPST_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return TPST_OK;
+}
+
+// ---- the pairing's Fq12 engines (tpst_selftest_tower) ----------------------
+// The engines' own code on caller-chosen operands: rns::load / load_res /
+// stage<OP> / store / store_res and rc_inv in the production kernels' shape
+// (12 waves, two elements per workgroup, an odd n's last workgroup running
+// its lone element in both halves as k_g2_prepare_rns does), wave::run with
+// the FE op set and fe_inv, one wave per element.  No arithmetic of its own.
+constexpr int TW_SLOTS = rns::N_CONSTS + 36 + 24;  // constants, A, B, C, rc_inv's temporaries
+
+template <int TOP>
+__device__ __forceinline__ void tower_rns_op(const rns::Eng& e, const rns::Lane& L, int A, int B, int C, int I,
+                                             Fq* sh_n) {
+  if constexpr (TOP == st::T_F12_MUL)
+    rns::stage<rns::OP_F12_MUL>(e, L, A, B, C);
+  else if constexpr (TOP == st::T_F12_SQR)
+    rns::stage<rns::OP_F12_SQR>(e, L, A, 0, C);
+  else if constexpr (TOP == st::T_CYC_SQR)
+    rns::stage<rns::OP_CYC_SQR>(e, L, A, 0, C);
+  else if constexpr (TOP == st::T_FROB1)
+    rns::stage<rns::OP_FROB1>(e, L, A, 0, C);
+  else if constexpr (TOP == st::T_FROB2)
+    rns::stage<rns::OP_FROB2>(e, L, A, 0, C);
+  else if constexpr (TOP == st::T_FROB3)
+    rns::stage<rns::OP_FROB3>(e, L, A, 0, C);
+  else if constexpr (TOP == st::T_CONJ)
+    rns::stage<rns::OP_CONJ>(e, L, A, 0, C);
+  else if constexpr (TOP == st::T_COPY)
+    rns::stage<rns::OP_COPY>(e, L, A, 0, C);
+  else
+    rc_inv(e, L, A, I, C, sh_n);
+}
+
+template <int TOP>
+__global__ void __launch_bounds__(64 * RC_WAVES) k_selftest_rns(int cin, int cout, size_t n,
+                                                                const uint32_t* __restrict__ a,
+                                                                const uint32_t* __restrict__ b,
+                                                                uint32_t* __restrict__ out) {
+  __shared__ uint32_t s_slots[TW_SLOTS * rns::SLOT];
+  __shared__ uint32_t s_xch[RC_WAVES * rns::XCH];
+  __shared__ Fq sh_n[2];
+  const size_t p0 = 2 * (size_t)blockIdx.x, p1 = p0 + 1 < n ? p0 + 1 : p0;
+  rns::load_consts((rns::lds_t*)s_slots);
+  const rns::Lane L = rns::load_lane();
+  const rns::Eng e{(rns::lds_t*)s_slots, (rns::lds_t*)s_xch + rns::wave_id() * rns::XCH, 0};
+  __syncthreads();
+  const int A = rns::N_CONSTS, B = A + 12, C = TOP == st::T_PASS ? A : A + 24, I = A + 36;
+  constexpr size_t WF = st::TOWER_FQ_WORDS, WR = st::TOWER_RES_WORDS;
+  if (cin == st::TW_FQ) {
+    rns::load(e, L, reinterpret_cast<const Fq*>(a + WF * p0), reinterpret_cast<const Fq*>(a + WF * p1), A, 12);
+    if constexpr (TOP == st::T_F12_MUL)
+      rns::load(e, L, reinterpret_cast<const Fq*>(b + WF * p0), reinterpret_cast<const Fq*>(b + WF * p1), B, 12);
+  } else {
+    rns::load_res(e, a + WR * p0, a + WR * p1, A, 12);
+    if constexpr (TOP == st::T_F12_MUL) rns::load_res(e, b + WR * p0, b + WR * p1, B, 12);
+  }
+  if constexpr (TOP != st::T_PASS) tower_rns_op<TOP>(e, L, A, B, C, I, sh_n);
+  if (cout == st::TW_FQ)
+    rns::store(e, L, C, reinterpret_cast<Fq*>(out + WF * p0), reinterpret_cast<Fq*>(out + WF * p1), 12);
+  else
+    rns::store_res(e, C, out + WR * p0, out + WR * p1, 12);
+}
+
+constexpr size_t TWV_LDS = (size_t)(FW_PROG + (wave::N_CONSTS + 64 + 36 + 24) * wave::SLOT) * 4;
+static_assert(TWV_LDS <= 65536, "tower self-test wave kernel LDS");
+
+// fe: index into FE_SET of a single stage, or < 0 for fe_inv
+__global__ void __launch_bounds__(64) k_selftest_wave(int fe, size_t n, const Fq12* __restrict__ a,
+                                                      const Fq12* __restrict__ b, Fq12* __restrict__ out) {
+  extern __shared__ uint4 smem4[];
+  wave::lds_t* prog = (wave::lds_t*)(smem4);
+  wave::lds_t* vals = prog + FW_PROG;
+  wave::load_set(prog, FE_SET);
+  wave::load_consts(vals, 0);
+  __syncthreads();
+  const size_t i = blockIdx.x;
+  if (i >= n) return;
+  const wave::Eng e{vals, wave::N_CONSTS, 0};
+  const int A = wave::N_CONSTS + 64, B = A + 12, C = A + 24, I = A + 36;
+  wave::load_f12(vals, A, a + i);
+  wave::load_f12(vals, B, (b ? b : a) + i);
+  if (fe < 0)
+    fe_inv(e, prog, A, I, C);
+  else
+    wave::run(e, prog + FE_SET.off[fe], A, B, C);
+  wave::store_f12(vals, C, out + i);
+}
+
+static int tower_fe_index(int idx) {
+  switch (idx) {
+    case st::T_F12_MUL: return FE_MUL;
+    case st::T_CYC_SQR: return FE_CYC;
+    case st::T_FROB1: return FE_FROB1;
+    case st::T_FROB2: return FE_FROB2;
+    case st::T_CONJ: return FE_CONJ;
+    default: return -1;  // T_INV
+  }
+}
+
+extern "C" int tpst_selftest_tower(tpst_ctx* ctx, int op, size_t n, const uint64_t* a, const uint64_t* b,
+                                   uint64_t* out) {
+  if (!ctx || !n || n > ((size_t)1 << 16) || !a || !out || !st::tower_op_valid(op))
+    return fail(ctx, TPST_E_ARG, "bad argument");
+  if (!b && st::tower_reads_b(op)) return fail(ctx, TPST_E_ARG, "bad argument");
+  std::lock_guard<tpst::CtxMutex> lk(ctx->mu);
+  TPST_HIP(ctx, hipSetDevice(ctx->device));
+  const int eng = st::tower_engine(op), idx = st::tower_index(op);
+  const int cin = st::tower_codec_in(op), cout = st::tower_codec_out(op);
+  const size_t wa = st::tower_a_words(op), wb = st::tower_b_words(op), wo = st::tower_out_words(op);
+  const size_t nok = idx == st::T_GT_POW ? n + (n & 1) : 0;  // trailing membership words
+  hipStream_t s = ctx->stream;
+  ctx->io.reset();
+  TPST_HIP(ctx, ctx->io.reserve(Arena::need(n * wa, 4) + Arena::need(n * wb + 2, 4) + Arena::need(n * wo + nok, 4) +
+                                (idx == st::T_G2_PREPARE ? Arena::need(plan::prepare_words(n), 4) : 0)));
+  uint32_t* d_a = ctx->io.take<uint32_t>(n * wa);
+  uint32_t* d_b = ctx->io.take<uint32_t>(n * wb + 2);
+  uint32_t* d_o = ctx->io.take<uint32_t>(n * wo + nok);
+  TPST_HIP(ctx, hipMemcpyAsync(d_a, a, n * wa * 4, hipMemcpyHostToDevice, s));
+  if (wb) TPST_HIP(ctx, hipMemcpyAsync(d_b, b, n * wb * 4, hipMemcpyHostToDevice, s));
+  const Fq12* fa = reinterpret_cast<const Fq12*>(d_a);
+  Fq12* fo = reinterpret_cast<Fq12*>(d_o);
+  if (idx == st::T_G2_PREPARE) {
+    uint32_t* prep = ctx->io.take<uint32_t>(plan::prepare_words(n));
+    TPST_HIP(ctx, g2_prepare_batch(s, d_a, n, reinterpret_cast<LineCoeff*>(d_o), prep));
+  } else if (idx == st::T_FINAL_EXP) {
+    TPST_HIP(ctx, gt_prod_final(s, fa, 1, n, fo));
+  } else if (idx == st::T_GT_POW) {
+    TPST_HIP(ctx, hipMemsetAsync(d_o, 0, (n * wo + nok) * 4, s));
+    TPST_HIP(ctx, gt_pow_wave(s, fa, reinterpret_cast<const uint64_t*>(d_b), n, fo, d_o + n * wo));
+  } else if (eng == st::TE_WAVE) {
+    k_selftest_wave<<<(unsigned)n, 64, TWV_LDS, s>>>(tower_fe_index(idx), n, fa,
+                                                     wb ? reinterpret_cast<const Fq12*>(d_b) : nullptr, fo);
+    TPST_HIP(ctx, hipGetLastError());
+  } else {
+    const unsigned grid = (unsigned)((n + 1) / 2);
+#define TPST_ST_TOWER(T) \
+  case T: k_selftest_rns<T><<<grid, 64 * RC_WAVES, 0, s>>>(cin, cout, n, d_a, d_b, d_o); break;
+    switch (idx) {
+      TPST_ST_TOWER(st::T_F12_MUL) TPST_ST_TOWER(st::T_F12_SQR) TPST_ST_TOWER(st::T_CYC_SQR)
+      TPST_ST_TOWER(st::T_FROB1) TPST_ST_TOWER(st::T_FROB2) TPST_ST_TOWER(st::T_FROB3)
+      TPST_ST_TOWER(st::T_CONJ) TPST_ST_TOWER(st::T_COPY) TPST_ST_TOWER(st::T_INV) TPST_ST_TOWER(st::T_PASS)
+      default: return fail(ctx, TPST_E_ARG, "bad argument");
+    }
+#undef TPST_ST_TOWER
+    TPST_HIP(ctx, hipGetLastError());
+  }
+  TPST_HIP(ctx, hipMemcpyAsync(out, d_o, (n * wo + nok) * 4, hipMemcpyDeviceToHost, s));
+  TPST_HIP(ctx, hipStreamSynchronize(s));
   return TPST_OK;
 }

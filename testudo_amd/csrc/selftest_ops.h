@@ -263,5 +263,65 @@ TPST_HD bool curve_lane_op(int op, const uint32_t* p, const uint32_t* q, uint32_
   }
 }
 
+// ---- tower ops (tpst_selftest_tower): op = engine << 8 | in codec << 7 | out codec << 6 | index
+// The pairing's two Fq12 engines on caller-chosen operands: the RNS chain
+// engine (rns_engine.h: 12 waves and two elements per workgroup) and the
+// radix wave engine (wave_tower.h: one wave per element).  Codecs (RNS engine
+// only; the wave engine is TW_FQ in and out): TW_FQ = field.h Montgomery Fq12
+// in tower order, 144 words, through rns::load (k = 1) / rns::store, or
+// wave::load_f12 / store_f12; TW_RES = 12 x 32 raw residue words (channel
+// lane & 31 of every coefficient's slot, any slot integer < 16 p) through
+// rns::load_res / store_res.
+enum : int { TE_RNS = 0, TE_WAVE = 1, N_TE = 2 };
+enum : int { TW_FQ = 0, TW_RES = 1 };
+// single stages (a, b -> out; b is read by T_F12_MUL and T_GT_POW only), then
+// the composites: T_INV the engines' Fq12 inversion (rc_inv / fe_inv, the head
+// of both final exponentiations), T_FINAL_EXP gt_prod_final with W = 1,
+// T_G2_PREPARE g2_prepare_batch (a = n affine G2 points, 48 words each; out =
+// 69 LineCoeff per point, coefficient-major: coefficient idx of point i at
+// out + 72 (idx n + i)), T_GT_POW gt_pow_wave (a = base, b = 4 u64 base-x
+// digits, 8 words; out = n x 144 result words, then n membership words ok[i],
+// then one zero word when n is odd; the result of an element with ok == 0 is
+// left zero), T_PASS no stage at all (RNS engine: the load straight into the
+// store, so FQ -> RES is rns::load alone and RES -> FQ rns::store alone on the
+// caller's slot integers)
+enum : int {
+  T_F12_MUL, T_F12_SQR, T_CYC_SQR, T_FROB1, T_FROB2, T_FROB3, T_CONJ, T_COPY, T_INV, T_FINAL_EXP, T_G2_PREPARE,
+  T_GT_POW, T_PASS, T_N
+};
+constexpr int TOWER_FQ_WORDS = 144, TOWER_RES_WORDS = 12 * 32, TOWER_G2_WORDS = 48, TOWER_LINES_WORDS = 69 * 72;
+
+TPST_HD int tower_engine(int op) { return op >> 8; }
+TPST_HD int tower_codec_in(int op) { return (op >> 7) & 1; }
+TPST_HD int tower_codec_out(int op) { return (op >> 6) & 1; }
+TPST_HD int tower_index(int op) { return op & 63; }
+TPST_HD int tower_op(int engine, int cin, int cout, int idx) { return engine << 8 | cin << 7 | cout << 6 | idx; }
+
+TPST_HD bool tower_op_valid(int op) {
+  if (op < 0) return false;
+  const int e = tower_engine(op), i = tower_index(op);
+  const bool fq = tower_codec_in(op) == TW_FQ && tower_codec_out(op) == TW_FQ;
+  if (e == TE_RNS) return i <= T_INV || i == T_PASS || (fq && (i == T_FINAL_EXP || i == T_G2_PREPARE));
+  if (e == TE_WAVE)
+    return fq && (i == T_F12_MUL || i == T_CYC_SQR || i == T_FROB1 || i == T_FROB2 || i == T_CONJ || i == T_INV ||
+                  i == T_GT_POW);
+  return false;
+}
+TPST_HD bool tower_reads_b(int op) { return tower_index(op) == T_F12_MUL || tower_index(op) == T_GT_POW; }
+// u32 words per element of a, of b (0: b is not read and may be null) and of
+// the result (T_GT_POW: without the n + (n & 1) trailing membership words)
+TPST_HD int tower_a_words(int op) {
+  if (tower_index(op) == T_G2_PREPARE) return TOWER_G2_WORDS;
+  return tower_codec_in(op) == TW_RES ? TOWER_RES_WORDS : TOWER_FQ_WORDS;
+}
+TPST_HD int tower_b_words(int op) {
+  if (!tower_reads_b(op)) return 0;
+  return tower_index(op) == T_GT_POW ? 8 : tower_a_words(op);
+}
+TPST_HD int tower_out_words(int op) {
+  if (tower_index(op) == T_G2_PREPARE) return TOWER_LINES_WORDS;
+  return tower_codec_out(op) == TW_RES ? TOWER_RES_WORDS : TOWER_FQ_WORDS;
+}
+
 }  // namespace selftest
 }  // namespace tpst

@@ -218,6 +218,24 @@ class Context:
                                                 _u32ptr(out)), "tpst_selftest_curve")
         return out
 
+    def selftest_tower(self, op: int, a: np.ndarray, b: np.ndarray = None):
+        """one operation of the pairing's RNS or wave Fq12 engine per row of a
+        (and b): `op` = selftest_tower_op(engine, name, cin, cout), rows are
+        u32 words (selftest_tower_words), the result is (n, out words) u32;
+        gt_pow returns (result, ok) with ok (n,) u32"""
+        wa, wb, wo = selftest_tower_words(op)
+        a = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1, wa)
+        n = len(a)
+        if wb:
+            b = np.ascontiguousarray(b, dtype=np.uint32).reshape(-1, wb)
+            assert len(b) == n
+        nok = n + (n & 1) if (op & 63) == SELFTEST_TOWER_OPS["gt_pow"] else 0
+        out = np.zeros(n * wo + nok, dtype=np.uint32)
+        self.check(self.lib.tpst_selftest_tower(self.h, op, n, _u32ptr(a), _u32ptr(b) if wb else None, _u32ptr(out)),
+                   "tpst_selftest_tower")
+        res = out[:n * wo].reshape(n, wo)
+        return (res, out[n * wo:n * wo + n]) if nok else res
+
 
 def _u32ptr(a: np.ndarray):
     assert a.dtype == np.uint32 and a.flags["C_CONTIGUOUS"] and a.size % 2 == 0
@@ -274,6 +292,50 @@ def selftest_curve_words(op: int) -> int:
     if SELFTEST_CURVE_UNIT <= form <= SELFTEST_CURVE_UNIT + 3:
         form -= SELFTEST_CURVE_UNIT
     return 8 if form == 7 else 96 if form in (3, 5, 6, 9) else 48
+
+
+# tpst_selftest_tower: op = engine << 8 | in codec << 7 | out codec << 6 | index (csrc/selftest_ops.h's tower_*
+# functions are the source; tests/test_tower_vectors.py compares these tables with the compiled header)
+SELFTEST_TOWER_ENGINES = {"rns": 0, "wave": 1}
+SELFTEST_TOWER_CODECS = {"fq": 0, "res": 1}
+SELFTEST_TOWER_OPS = {"f12_mul": 0, "f12_sqr": 1, "cyc_sqr": 2, "frob1": 3, "frob2": 4, "frob3": 5, "conj": 6,
+                      "copy": 7, "inv": 8, "final_exp": 9, "g2_prepare": 10, "gt_pow": 11, "pass": 12}
+# what each engine runs; final_exp and g2_prepare take the fq codec only
+SELFTEST_TOWER_ENGINE_OPS = {
+    "rns": ("f12_mul", "f12_sqr", "cyc_sqr", "frob1", "frob2", "frob3", "conj", "copy", "inv", "final_exp",
+            "g2_prepare", "pass"),
+    "wave": ("f12_mul", "cyc_sqr", "frob1", "frob2", "conj", "inv", "gt_pow"),
+}
+
+
+def selftest_tower_op(engine: str, name: str, cin: str = "fq", cout: str = "fq") -> int:
+    assert name in SELFTEST_TOWER_ENGINE_OPS[engine]
+    assert (cin == "fq" and cout == "fq") or (engine == "rns" and name not in ("final_exp", "g2_prepare"))
+    return (SELFTEST_TOWER_ENGINES[engine] << 8 | SELFTEST_TOWER_CODECS[cin] << 7 | SELFTEST_TOWER_CODECS[cout] << 6 |
+            SELFTEST_TOWER_OPS[name])
+
+
+def selftest_tower_valid(op: int) -> bool:
+    if op < 0:
+        return False
+    eng, idx, fq = op >> 8, op & 63, (op >> 6) & 3 == 0
+    names = {v: k for k, v in SELFTEST_TOWER_OPS.items()}
+    for e, num in SELFTEST_TOWER_ENGINES.items():
+        if eng == num:
+            return (idx in names and names[idx] in SELFTEST_TOWER_ENGINE_OPS[e] and
+                    (fq or (e == "rns" and names[idx] not in ("final_exp", "g2_prepare"))))
+    return False
+
+
+def selftest_tower_words(op: int):
+    """u32 words per element of a, of b (0: not read) and of the result (gt_pow:
+    without the trailing membership words) of a tpst_selftest_tower op"""
+    idx = op & 63
+    if idx == SELFTEST_TOWER_OPS["g2_prepare"]:
+        return 48, 0, 69 * 72
+    wa = 384 if (op >> 7) & 1 else 144
+    wb = 8 if idx == SELFTEST_TOWER_OPS["gt_pow"] else wa if idx == SELFTEST_TOWER_OPS["f12_mul"] else 0
+    return wa, wb, (384 if (op >> 6) & 1 else 144)
 
 
 class Gens:
