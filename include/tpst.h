@@ -344,7 +344,9 @@ int tpst_transcript_append_bytes(tpst_transcript* t, const uint8_t* bytes, size_
  * R1CSInstance (r1csinstance.rs): num_cons x (2 num_vars) sparse A, B, C;
  * z = vars || 1 || inputs || 0.  Matrices as (row u32, col u32, canonical Fr)
  * triples, any order; kept on the device as CSR (multiply_vec) + CSC
- * (compute_eval_table_sparse). */
+ * (compute_eval_table_sparse).  num_cons and num_vars are powers of two >= 2;
+ * the provers over the witness (tpst_r1cs_prove, tpst_groth16_setup) and
+ * tpst_r1cs_synthetic need num_vars >= 4. */
 typedef struct tpst_r1cs tpst_r1cs;
 int tpst_r1cs_load(tpst_ctx* ctx, size_t num_cons, size_t num_vars, size_t num_inputs, const size_t* nnz /*[3]*/,
                    const uint32_t* const* rows /*[3]*/, const uint32_t* const* cols /*[3]*/,
@@ -577,6 +579,102 @@ int tpst_prodcircuit_verify(int ell, size_t P, size_t D, const uint64_t* claims_
                             const uint64_t* proof, tpst_transcript_fr* tr, uint64_t* claims_out,
                             uint64_t* claims_dotp_out, uint64_t* rand);
 
+/* ---- SPARK evaluation proofs (csrc/sparse_eval.hip) --------------------------
+ * R1CSEvalProof = SparseMatPolyEvalProof::{prove, verify} (r1csinstance.rs:
+ * 336-386, sparse_mlpoly.rs:1441-1569): the opening of the computational
+ * commitment of tpst_r1cs_commit at (rx, ry), over PoseidonTranscript<Fr>.
+ * Unblinded, as the reference (it passes None); batch size 3 = (A, B, C).
+ *
+ * Dimensions.  N = num_nz_entries.next_power_of_two() ops per matrix (>= 2),
+ * cells = max(num_cons, 2 num_vars) memory cells; comb_ops has ell_ops = log2 N
+ * + 4 variables, comb_mem ell_mem = log2 cells + 1, comb_derefs ell_derefs =
+ * log2 N + 3; a polynomial of ell variables is committed as 2^(ell / 2) rows.
+ * rx has log2(num_cons) entries, ry log2(2 num_vars), MSB-first. */
+/* R1CSCommitmentGens::setup (r1csinstance.rs:33-52, sparse_mlpoly.rs:296-323):
+ * the three Hyrax generator sets (ops, mem, derefs), each tpst_gens_new(R + 1,
+ * label) loaded over its first R points with h, Q = G[R]; built once here.
+ * TPST_E_ARG: dimensions that are not powers of two, num_inputs >= num_vars,
+ * fewer than 2 entries. */
+typedef struct tpst_r1cs_gens tpst_r1cs_gens;
+int tpst_r1cs_gens_setup(tpst_ctx* ctx, const uint8_t* label, size_t label_len, size_t num_cons, size_t num_vars,
+                         size_t num_inputs, size_t num_nz_entries, tpst_r1cs_gens** out);
+void tpst_r1cs_gens_free(tpst_r1cs_gens* gens);
+/* R1CSDecommitment (MultiSparseMatPolynomialAsDense) on the device: comb_ops
+ * (16 N canonical Fr: row.ops_addr | row.read_ts | col.ops_addr | col.read_ts |
+ * val | 0), comb_mem (row.audit_ts | col.audit_ts) and the addresses and
+ * timestamps as u32. */
+typedef struct tpst_r1cs_decomm tpst_r1cs_decomm;
+/* R1CSInstance::commit (r1csinstance.rs:313-333) over `gens`, keeping the
+ * decommitment: comm_ops / comm_mem as tpst_r1cs_commit returns them for the
+ * same label; with comm_ops or comm_mem NULL only the row counts are reported.
+ * TPST_E_ARG: an instance or generators of another context, generators of
+ * another shape. */
+int tpst_r1cs_commit_decomm(tpst_ctx* ctx, tpst_r1cs* r1cs, const tpst_r1cs_gens* gens, uint64_t* comm_ops,
+                            size_t* ops_rows, uint64_t* comm_mem, size_t* mem_rows, tpst_r1cs_decomm** out);
+void tpst_r1cs_decomm_free(tpst_r1cs_decomm* decomm);
+
+/* The fixed-size part of the proof, canonical Fr.  The variable parts are
+ * caller-owned buffers: comm_derefs (derefs_rows G1 points) and the two flat
+ * product-circuit proofs, laid out as tpst_prodcircuit_proof_len defines them:
+ * prod_ops for (log2 N, 12, 6), prod_mem for (log2 cells, 4, 0). */
+typedef struct {
+  /* ProductLayerProof: eval_row / eval_col = init, read A B C, write A B C,
+   * audit; eval_val = the split dot-product claims, [0] left, [1] right */
+  uint64_t prod_row[8][4], prod_col[8][4], prod_val[2][3][4];
+  /* HashLayerProof: eval_row / eval_col = ops_addr A B C, read_ts A B C,
+   * audit_ts; eval_val; eval_derefs = [0] row_ops_val, [1] col_ops_val */
+  uint64_t hash_row[7][4], hash_col[7][4], hash_val[3][4], hash_derefs[2][3][4];
+  /* DerefsEvalProof.proof_derefs, HashLayerProof.proof_ops / proof_mem */
+  tpst_dotprod_proof proof_derefs, proof_ops, proof_mem;
+} tpst_r1cs_eval_proof;
+typedef struct {
+  size_t num_ops, num_mem_cells;            /* N, cells */
+  int32_t ell_ops, ell_mem, ell_derefs;     /* variables of the three committed polynomials */
+  int32_t log_ops, log_cells;               /* ell of the two batched product proofs */
+  size_t ops_rows, mem_rows, derefs_rows;   /* G1 points of comm_ops / comm_mem / comm_derefs */
+  size_t prod_ops_len, prod_mem_len;        /* Fr of the two flat product proofs */
+  size_t rnd_len[3];                        /* Fr of the draws, in proving order: derefs, ops, mem */
+} tpst_r1cs_eval_sizes;
+/* host only, no context; TPST_E_ARG for dimensions tpst_r1cs_gens_setup rejects */
+int tpst_r1cs_eval_proof_sizes(size_t num_cons, size_t num_vars, size_t num_nz_entries, tpst_r1cs_eval_sizes* out);
+/* SparseMatPolyEvalProof::prove (sparse_mlpoly.rs:1473-1532): evals = 3 Fr =
+ * (A, B, C)(rx, ry); rnd_derefs / rnd_ops / rnd_mem = the reference's
+ * thread_rng draws of the three openings in proving order, each 3 + 4 log2(R_k)
+ * Fr as tpst_hyrax_eval_prove documents.  `tr` is updated in place, and only on
+ * success.  The eq tables, the dereference, the hash layer, both batched
+ * product proofs, the 23 evaluations and the three openings run on the device.
+ * TPST_E_ARG: a null argument, a value >= r, a handle of another context,
+ * generators of another shape, or one of the prover's assertions (the message
+ * says which): init * writes != reads * audit over the rows or the columns,
+ * left + right != evals[m]. */
+int tpst_r1cs_eval_prove(tpst_ctx* ctx, const tpst_r1cs_decomm* decomm, const tpst_r1cs_gens* gens,
+                         const uint64_t* rx, const uint64_t* ry, const uint64_t* evals, const uint64_t* rnd_derefs,
+                         const uint64_t* rnd_ops, const uint64_t* rnd_mem, tpst_transcript_fr* tr,
+                         tpst_r1cs_eval_proof* proof, uint64_t* comm_derefs, uint64_t* prod_ops, uint64_t* prod_mem);
+/* SparseMatPolyEvalProof::verify (sparse_mlpoly.rs:1534-1568 with :1377-1438,
+ * :1238-1334, :896-1040): needs no instance and no decommitment.  The
+ * transcript, both tpst_prodcircuit_verify, the subset and claim checks and the
+ * n-to-1 reductions are host work; the three tpst_hyrax_eval_verify_plain run
+ * on the device.  `tr` is updated in place, and only on success.
+ * TPST_E_VERIFY: any failed check of the reference's verifier, or any Fr (of
+ * the proof, evals, rx, ry) or point (of the proof or the commitment) that is
+ * non-canonical, off the curve or outside the subgroup, all checked before the
+ * transcript absorbs anything.  TPST_E_ARG: a null argument, generators of
+ * another context, num_ops / num_mem_cells that do not match the generators. */
+int tpst_r1cs_eval_verify(tpst_ctx* ctx, const uint64_t* comm_ops, const uint64_t* comm_mem, size_t num_ops,
+                          size_t num_mem_cells, const tpst_r1cs_gens* gens, const uint64_t* rx, const uint64_t* ry,
+                          const uint64_t* evals, tpst_transcript_fr* tr, const tpst_r1cs_eval_proof* proof,
+                          const uint64_t* comm_derefs, const uint64_t* prod_ops, const uint64_t* prod_mem);
+/* The prover's stages alone (tests, tools); any output may be NULL.  derefs:
+ * comb_derefs, 8 N Fr; r_mem_check = (r_hash, gamma) -> hash_ops: 12 N Fr (row
+ * read | row write | col read | col write, A B C each) and hash_mem: 4 cells
+ * (row init | row audit | col init | col audit); seg: the 15 evaluations of
+ * comb_ops' segments and the 6 of comb_derefs' at rand_ops (log2 N Fr), then
+ * the 2 of comb_mem's halves at rand_mem (log2 cells Fr). */
+int tpst_r1cs_eval_stages(tpst_ctx* ctx, const tpst_r1cs_decomm* decomm, const uint64_t* rx, const uint64_t* ry,
+                          const uint64_t* r_mem_check, const uint64_t* rand_ops, const uint64_t* rand_mem,
+                          uint64_t* derefs, uint64_t* hash_ops, uint64_t* hash_mem, uint64_t* seg);
+
 /* ---- Groth16 over BLS12-377 (csrc/groth16.hip) ----
  * The prover behind R1CSProof::prove_verifier (r1csproof.rs:374-434,
  * Groth16::<E>::prove at :421): ark-groth16 create_proof with the
@@ -709,7 +807,9 @@ int tpst_selftest_tower(tpst_ctx* ctx, int op, size_t n, const uint64_t* a, cons
  * (first launch to last result, the host work between launches included);
  * 20 / 21: tpst_prodcircuit_prove's layer build / all layer proofs (host work
  * between launches included); 22 / 23: round 0 / round 1 of its layer 0 alone
- * (round kernel and reduce). */
+ * (round kernel and reduce); 24 / 25 / 26 / 27: tpst_r1cs_eval_prove's
+ * k_deref / k_hash_ops / k_hash_mem / k_seg_eval (both groups, with their
+ * partial sums). */
 int tpst_profile_enable(tpst_ctx* ctx, int on);
 int tpst_profile_reset(tpst_ctx* ctx);
 int tpst_profile_read(tpst_ctx* ctx, int stage, double* total_ms, uint64_t* launches);

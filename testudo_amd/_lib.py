@@ -130,6 +130,17 @@ PROTOTYPES = [
     ("tpst_prodcircuit_prove_dev", C.c_int, [_vp, C.c_int, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _u64p, _u64p, _u64p,
                                              _u64p]),
     ("tpst_prodcircuit_verify", C.c_int, [C.c_int, _sz, _sz, _u64p, _u64p, _u64p, _vp, _u64p, _u64p, _u64p]),
+    ("tpst_r1cs_gens_setup", C.c_int, [_vp, C.c_char_p, _sz, _sz, _sz, _sz, _sz, C.POINTER(_vp)]),
+    ("tpst_r1cs_gens_free", None, [_vp]),
+    ("tpst_r1cs_commit_decomm", C.c_int, [_vp, _vp, _vp, _u64p, C.POINTER(_sz), _u64p, C.POINTER(_sz),
+                                          C.POINTER(_vp)]),
+    ("tpst_r1cs_decomm_free", None, [_vp]),
+    ("tpst_r1cs_eval_proof_sizes", C.c_int, [_sz, _sz, _sz, _vp]),
+    ("tpst_r1cs_eval_prove", C.c_int, [_vp, _vp, _vp, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p, _vp, _vp, _u64p,
+                                       _u64p, _u64p]),
+    ("tpst_r1cs_eval_verify", C.c_int, [_vp, _u64p, _u64p, _sz, _sz, _vp, _u64p, _u64p, _u64p, _vp, _vp, _u64p,
+                                        _u64p, _u64p]),
+    ("tpst_r1cs_eval_stages", C.c_int, [_vp, _vp, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p]),
     ("tpst_groth16_setup", C.c_int, [_vp, _vp, _u64p, C.POINTER(_vp)]),
     ("tpst_groth16_pk_free", None, [_vp]),
     ("tpst_groth16_domain", C.c_int, [_vp, C.POINTER(_sz)]),
@@ -221,6 +232,29 @@ class DotProdProof(C.Structure):
         ("R", (C.c_uint64 * 12) * HYRAX_MAX_ROUNDS),
         ("delta", C.c_uint64 * 12), ("beta", C.c_uint64 * 12),
         ("z1", C.c_uint64 * 4), ("z2", C.c_uint64 * 4),
+    ]
+
+
+class R1CSEvalProof(C.Structure):
+    """tpst_r1cs_eval_proof: the fixed-size part of R1CSEvalProof."""
+    _fields_ = [
+        ("prod_row", (C.c_uint64 * 4) * 8), ("prod_col", (C.c_uint64 * 4) * 8),
+        ("prod_val", ((C.c_uint64 * 4) * 3) * 2),
+        ("hash_row", (C.c_uint64 * 4) * 7), ("hash_col", (C.c_uint64 * 4) * 7),
+        ("hash_val", (C.c_uint64 * 4) * 3), ("hash_derefs", ((C.c_uint64 * 4) * 3) * 2),
+        ("proof_derefs", DotProdProof), ("proof_ops", DotProdProof), ("proof_mem", DotProdProof),
+    ]
+
+
+class R1CSEvalSizes(C.Structure):
+    """tpst_r1cs_eval_sizes"""
+    _fields_ = [
+        ("num_ops", _sz), ("num_mem_cells", _sz),
+        ("ell_ops", C.c_int32), ("ell_mem", C.c_int32), ("ell_derefs", C.c_int32),
+        ("log_ops", C.c_int32), ("log_cells", C.c_int32),
+        ("ops_rows", _sz), ("mem_rows", _sz), ("derefs_rows", _sz),
+        ("prod_ops_len", _sz), ("prod_mem_len", _sz),
+        ("rnd_len", _sz * 3),
     ]
 
 

@@ -316,6 +316,7 @@ static hipError_t ntt(hipStream_t s, uint32_t* a, size_t n, int lg, const uint32
 extern "C" int tpst_groth16_setup(tpst_ctx* ctx, tpst_r1cs* R, const uint64_t* toxic, tpst_groth16_pk** out) {
   if (!ctx || !R || !toxic || !out) return setup_fail(ctx, "null argument");
   if (R->owner != ctx) return setup_fail(ctx, "instance belongs to another context");
+  if (R->num_vars < 4) return setup_fail(ctx, "num_vars must be >= 4");
   *out = nullptr;
   for (int k = 0; k < 5; k++) {
     if (!fr_ok(toxic + 4 * k)) return setup_fail(ctx, "toxic waste value >= r");

@@ -49,6 +49,9 @@ enum MsmStage {
   // evaluations); every layer proof from the first squeeze to the last claims (the host's transcript between
   // launches included); round 0 / round 1 of layer 0 alone (round kernel + reduce: the bandwidth-bound rounds)
   ST_PRODTREE_BUILD, ST_PRODTREE_ROUNDS, ST_PRODTREE_ROUND0, ST_PRODTREE_ROUND1,
+  // tpst_r1cs_eval_prove: the memory dereference; the hash layer over the ops and over the cells; the segmented
+  // multi-evaluation (both groups, partial sums included)
+  ST_SPARSE_DEREF, ST_SPARSE_HASH_OPS, ST_SPARSE_HASH_MEM, ST_SPARSE_SEG_EVAL,
   N_STAGES
 };
 

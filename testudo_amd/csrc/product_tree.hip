@@ -37,6 +37,7 @@
 #include "ctx.h"
 #include "device_util.h"
 #include "fr_sponge.h"
+#include "product_tree.h"
 #include "pst_kernels.h"
 #include "r1cs_state.h"
 
@@ -272,54 +273,71 @@ bool dims_ok(int ell, size_t P, size_t D) {
   return ell >= 1 && ell <= 30 && P >= 1 && (D & 1) == 0 && P <= PT_MAX_INSTANCES && D <= PT_MAX_INSTANCES - P;
 }
 
+}  // namespace
+
 // ------------------------------------------------------------- prover ----
 // ProductCircuitEvalProofBatched::prove (product_tree.rs:255-377) over device
-// inputs (canonical Fr).  The caller holds the context lock.
-int prove_locked(tpst_ctx* ctx, int ell, size_t P, const uint32_t* d_polys, size_t D, const uint32_t* d_left,
-                 const uint32_t* d_right, const uint32_t* d_weight, tpst_transcript_fr* tr, uint64_t* proof,
-                 uint64_t* claims_prod, uint64_t* claims_dotp, uint64_t* rand_out) {
+// inputs (canonical Fr), in two steps (product_tree.h): build allocates the
+// arena, builds every layer and returns the claims; rounds runs the layer
+// proofs.  The caller holds the context lock.
+namespace {
+// pinned staging: sums down | challenge up | layer block up | finals and claims down
+struct Pins {
+  uint64_t (*hs)[4];
+  Fr* rpin;
+  Fr* laypin;
+  uint64_t (*finpin)[4];
+};
+int pins_for(tpst_ctx* ctx, int ell, size_t P, size_t D, Pins& pn) {
+  const size_t NI = P + D;
+  const size_t pin_lay = 256, pin_fin = pin_lay + 32 * ((size_t)ell + NI), pin_end = pin_fin + 32 * (2 * NI + D + P + 3 * D);
+  if (int rc = ensure_pinned(ctx, pin_end)) return rc;
+  char* const pin = (char*)ctx->pinned;
+  pn.hs = reinterpret_cast<uint64_t(*)[4]>(pin);
+  pn.rpin = reinterpret_cast<Fr*>(pin + 128);
+  pn.laypin = reinterpret_cast<Fr*>(pin + pin_lay);
+  pn.finpin = reinterpret_cast<uint64_t(*)[4]>(pin + pin_fin);
+  return TPST_OK;
+}
+}  // namespace
+
+int tpst::ProdCircuitProver::build(tpst_ctx* ctx, int ell_, size_t P_, const uint32_t* d_polys, size_t D_,
+                                   const uint32_t* d_left, const uint32_t* d_right, const uint32_t* d_weight,
+                                   uint64_t* claims_prod, uint64_t* claims_dotp) {
+  ell = ell_, P = P_, D = D_;
   hipStream_t s = ctx->stream;
-  FrSponge sp;
-  if (!sp.load(tr)) return fail(ctx, TPST_E_ARG, "bad transcript state");
-  const Layout lay(ell, P, D);
   const size_t N = (size_t)1 << ell, nh = N >> 1, NI = P + D;
   // ---- the arena, in Fr: every layer (layer k: P buffers of 2^(ell - k), k =
   // ell the products themselves), the dot-product tables, the eq ping-pong
   // pair and its scratch, partials, and the small per-round / per-layer slots
-  std::vector<size_t> loff(ell + 2);
+  loff.assign(ell + 2, 0);
   size_t off = 0;
   for (int k = 0; k <= ell; k++) {
     loff[k] = off;
     off += P * (N >> k);
   }
-  const size_t o_dot = off;
+  o_dot = off;
   off += 3 * D * nh;
-  const size_t o_eq = off;
+  o_eq = off;
   off += 2 * nh;
-  const size_t o_eqs = off;
+  o_eqs = off;
   off += eq_table_scratch(ell - 1);
-  const size_t o_part = off;
+  o_part = off;
   off += 3 * NI * PT_MAX_BLOCKS;
-  const size_t o_sums = off;  // 3: the round's combined sums; 3 D: the dot products' evaluations
+  o_sums = off;  // 3: the round's combined sums; 3 D: the dot products' evaluations
   off += 3 + 3 * D;
-  const size_t o_r = off;  // the round's challenge
+  o_r = off;  // the round's challenge
   off += 1;
-  const size_t o_lay = off;  // rand | coeffs of the layer
+  o_lay = off;  // rand | coeffs of the layer
   off += (size_t)ell + NI;
-  const size_t o_fin = off;  // left | right | weight final claims
+  o_fin = off;  // left | right | weight final claims
   off += 2 * NI + D;
-  DevBuf arena;
   TPST_HIP(ctx, arena.alloc(off * 32));
   uint32_t* const base = arena.u();
   const auto at = [&](size_t o) { return base + 8 * o; };
-  // pinned staging: sums down | challenge up | layer block up | finals and claims down
-  const size_t pin_lay = 256, pin_fin = pin_lay + 32 * ((size_t)ell + NI), pin_end = pin_fin + 32 * (2 * NI + D + P + 3 * D);
-  if (int rc = ensure_pinned(ctx, pin_end)) return rc;
-  char* const pin = (char*)ctx->pinned;
-  uint64_t(*hs)[4] = reinterpret_cast<uint64_t(*)[4]>(pin);
-  Fr* const rpin = reinterpret_cast<Fr*>(pin + 128);
-  Fr* const laypin = reinterpret_cast<Fr*>(pin + pin_lay);
-  uint64_t(*finpin)[4] = reinterpret_cast<uint64_t(*)[4]>(pin + pin_fin);
+  Pins pn;
+  if (int rc = pins_for(ctx, ell, P, D, pn)) return rc;
+  uint64_t(*const finpin)[4] = pn.finpin;
 
   Profiler& pf = ctx->prof;
   // ---- layers: Montgomery copies of the inputs, then one pass per layer
@@ -350,7 +368,8 @@ int prove_locked(tpst_ctx* ctx, int ell, size_t P, const uint32_t* d_polys, size
   TPST_HIP(ctx, hipMemcpyAsync(clpin, at(o_fin), P * 32, hipMemcpyDeviceToHost, s));
   if (D) TPST_HIP(ctx, hipMemcpyAsync(clpin + P, at(o_sums + 3), 3 * D * 32, hipMemcpyDeviceToHost, s));
   TPST_HIP(ctx, hipStreamSynchronize(s));
-  std::vector<Fr> claims(P), cdot(D);
+  claims.resize(P);
+  cdot.resize(D);
   for (size_t p = 0; p < P; p++) {
     memcpy(claims_prod + 4 * p, clpin[p], 32);
     claims[p] = fr_canon(clpin[p]);
@@ -359,6 +378,24 @@ int prove_locked(tpst_ctx* ctx, int ell, size_t P, const uint32_t* d_polys, size
     memcpy(claims_dotp + 4 * d, clpin[P + 3 * d], 32);
     cdot[d] = fr_canon(clpin[P + 3 * d]);
   }
+  return TPST_OK;
+}
+
+int tpst::ProdCircuitProver::rounds(tpst_ctx* ctx, tpst_transcript_fr* tr, uint64_t* proof, uint64_t* rand_out) {
+  hipStream_t s = ctx->stream;
+  FrSponge sp;
+  if (!sp.load(tr)) return fail(ctx, TPST_E_ARG, "bad transcript state");
+  const Layout lay(ell, P, D);
+  const size_t nh = (size_t)1 << (ell - 1);
+  uint32_t* const base = arena.u();
+  const auto at = [&](size_t o) { return base + 8 * o; };
+  Pins pn;
+  if (int rc = pins_for(ctx, ell, P, D, pn)) return rc;
+  uint64_t(*const hs)[4] = pn.hs;
+  Fr* const rpin = pn.rpin;
+  Fr* const laypin = pn.laypin;
+  uint64_t(*const finpin)[4] = pn.finpin;
+  Profiler& pf = ctx->prof;
 
   // ---- layer proofs, from the top (product_tree.rs:270-368): layer proof i
   // runs over circuit layer ell - 1 - i, whose sides have 2^i entries
@@ -444,6 +481,18 @@ int prove_locked(tpst_ctx* ctx, int ell, size_t P, const uint32_t* d_polys, size
   for (int j = 0; j < ell; j++) fr_out(rand[j], rand_out + 4 * j);
   sp.store(tr);
   return TPST_OK;
+}
+
+namespace {
+
+int prove_locked(tpst_ctx* ctx, int ell, size_t P, const uint32_t* d_polys, size_t D, const uint32_t* d_left,
+                 const uint32_t* d_right, const uint32_t* d_weight, tpst_transcript_fr* tr, uint64_t* proof,
+                 uint64_t* claims_prod, uint64_t* claims_dotp, uint64_t* rand_out) {
+  FrSponge sp;
+  if (!sp.load(tr)) return fail(ctx, TPST_E_ARG, "bad transcript state");
+  ProdCircuitProver pv;
+  if (int rc = pv.build(ctx, ell, P, d_polys, D, d_left, d_right, d_weight, claims_prod, claims_dotp)) return rc;
+  return pv.rounds(ctx, tr, proof, rand_out);
 }
 
 int prove_args(tpst_ctx* ctx, int ell, size_t P, const void* polys, size_t D, const void* l, const void* r,

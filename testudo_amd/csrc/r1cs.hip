@@ -26,6 +26,7 @@
 #include "device_util.h"
 #include "r1cs_state.h"
 #include "scan_sort.h"
+#include "sparse_eval_state.h"
 
 using namespace tpst;
 
@@ -495,8 +496,13 @@ static int r1cs_from_device(tpst_ctx* ctx, tpst_r1cs* R, const uint32_t* const r
   return TPST_OK;
 }
 
-static int r1cs_dims(tpst_ctx* ctx, size_t num_cons, size_t num_vars, size_t num_inputs) {
-  if (log2_exact(num_cons) < 1 || log2_exact(num_vars) < 2) return fail(ctx, TPST_E_ARG, "num_cons / num_vars must be powers of two (num_vars >= 4)");
+// min_var_bits: 2 where the witness is committed or proved over (the sqrt-PST
+// needs num_vars >= 4), 1 for an instance that is only loaded: the SPARK
+// commitment and its evaluation proof take any instance
+static int r1cs_dims(tpst_ctx* ctx, size_t num_cons, size_t num_vars, size_t num_inputs, int min_var_bits = 2) {
+  if (log2_exact(num_cons) < 1 || log2_exact(num_vars) < min_var_bits)
+    return fail(ctx, TPST_E_ARG, min_var_bits == 2 ? "num_cons / num_vars must be powers of two (num_vars >= 4)"
+                                                   : "num_cons / num_vars must be powers of two (>= 2)");
   if (num_inputs >= num_vars) return fail(ctx, TPST_E_ARG, "num_inputs + 1 must be <= num_vars");
   if (num_cons > ((size_t)1 << 31) || num_vars > ((size_t)1 << 30)) return fail(ctx, TPST_E_ARG, "instance too large");
   return TPST_OK;
@@ -506,7 +512,7 @@ extern "C" int tpst_r1cs_load(tpst_ctx* ctx, size_t num_cons, size_t num_vars, s
                               const size_t* nnz, const uint32_t* const* rows, const uint32_t* const* cols,
                               const uint64_t* const* vals, tpst_r1cs** out) {
   if (!ctx || !nnz || !rows || !cols || !vals || !out) return fail(ctx, TPST_E_ARG, "null argument");
-  if (int rc = r1cs_dims(ctx, num_cons, num_vars, num_inputs)) return rc;
+  if (int rc = r1cs_dims(ctx, num_cons, num_vars, num_inputs, 1)) return rc;
   std::lock_guard<tpst::CtxMutex> lk(ctx->mu);
   TPST_HIP(ctx, hipSetDevice(ctx->device));
   std::unique_ptr<tpst_r1cs> R(new tpst_r1cs());
@@ -686,6 +692,7 @@ extern "C" int tpst_r1cs_prove(tpst_ctx* ctx, tpst_r1cs* R, const uint64_t* vars
   if (R->owner != ctx) return fail(ctx, TPST_E_ARG, "instance belongs to another context");
   memset(out, 0, sizeof(*out));
   const int nvar_bits = log2_exact(R->num_vars);
+  if (nvar_bits < 2) return fail(ctx, TPST_E_ARG, "the witness commitment needs num_vars >= 4");
   const int rx_n = log2_exact(R->num_cons), ry_n = nvar_bits + 1;
   if (rx_n > TPST_R1CS_MAX_ROUNDS || ry_n > TPST_R1CS_MAX_ROUNDS || nvar_bits > 2 * TPST_MAX_VARS)
     return fail(ctx, TPST_E_ARG, "instance too large for tpst_r1cs_proof");
@@ -790,6 +797,70 @@ extern "C" int tpst_r1cs_prove(tpst_ctx* ctx, tpst_r1cs* R, const uint64_t* vars
   return TPST_OK;
 }
 
+// The SPARK dense representation alone (multi_sparse_to_dense_rep,
+// sparse_mlpoly.rs:373-437), shared by tpst_r1cs_commit below and
+// tpst_r1cs_commit_decomm (sparse_eval.hip): fills `d` on the context's
+// device and waits for it.
+int tpst::r1cs_dense_rep(tpst_ctx* ctx, tpst_r1cs* R, tpst_r1cs_decomm& d) {
+  size_t maxnz = 1;
+  for (int m = 0; m < 3; m++) maxnz = R->nnz[m] > maxnz ? R->nnz[m] : maxnz;
+  size_t N = 1;
+  while (N < maxnz) N <<= 1;
+  const int vx = log2_exact(R->num_cons), vy = log2_exact(R->ncols);
+  const int vmax = vx > vy ? vx : vy;
+  const size_t cells = (size_t)1 << vmax;
+  if (3 * N >= ((size_t)1 << 31)) return fail(ctx, TPST_E_ARG, "instance too large");
+  d.owner = ctx;
+  d.N = N, d.cells = cells, d.vx = vx, d.vy = vy;
+  d.num_cons = R->num_cons, d.num_vars = R->num_vars, d.num_inputs = R->num_inputs;
+  DevBuf& ops = d.ops;
+  DevBuf& mem = d.mem;
+  std::lock_guard<tpst::CtxMutex> lk(ctx->mu);
+  TPST_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const size_t M3 = 3 * N;
+  TPST_HIP(ctx, ops.alloc(16 * N * 32));
+  TPST_HIP(ctx, mem.alloc(2 * cells * 32));
+  TPST_HIP(ctx, hipMemsetAsync(ops.p, 0, 16 * N * 32, s));
+  DevBuf pos, skey, spos, tmp;
+  for (int rc = 0; rc < 2; rc++) {
+    TPST_HIP(ctx, d.addr[rc].alloc(M3 * 4));
+    TPST_HIP(ctx, d.rts[rc].alloc(M3 * 4));
+    TPST_HIP(ctx, d.audit[rc].alloc(cells * 4));
+  }
+  TPST_HIP(ctx, pos.alloc(M3 * 4));
+  TPST_HIP(ctx, skey.alloc(M3 * 4));
+  TPST_HIP(ctx, spos.alloc(M3 * 4));
+  TPST_HIP(ctx, tmp.alloc(scan_sort::sort_scratch(M3) * 4));
+  for (int rc = 0; rc < 2; rc++) {  // rows, then columns
+    const DevBuf* o = rc ? R->ocol : R->orow;
+    const DevBuf& addr = d.addr[rc];
+    const DevBuf& rts = d.rts[rc];
+    const DevBuf& audit = d.audit[rc];
+    k_ops_addr<<<grid_for(M3, 256), 256, 0, s>>>(o[0].u(), o[1].u(), o[2].u(), (uint32_t)R->nnz[0],
+                                                 (uint32_t)R->nnz[1], (uint32_t)R->nnz[2], N, addr.u(), pos.u());
+    TPST_HIP(ctx, hipGetLastError());
+    // stable by address: equal addresses keep position order (the timestamps' rank)
+    TPST_HIP(ctx, scan_sort::stable_sort_pairs(s, addr.u(), pos.u(), skey.u(), spos.u(), M3, vmax + 1, tmp.u()));
+    TPST_HIP(ctx, hipMemsetAsync(audit.p, 0, cells * 4, s));
+    k_timestamps<<<grid_for(M3, 256), 256, 0, s>>>(skey.u(), spos.u(), M3, rts.u(), audit.u());
+    TPST_HIP(ctx, hipGetLastError());
+    // comb_ops segments: row.ops_addr | row.read_ts | col.ops_addr | col.read_ts | val | 0
+    uint32_t* base = ops.u() + 8 * (size_t)(rc * 2) * M3;
+    k_u32_to_fr<<<grid_for(M3, 256), 256, 0, s>>>(addr.u(), M3, base);
+    k_u32_to_fr<<<grid_for(M3, 256), 256, 0, s>>>(rts.u(), M3, base + 8 * M3);
+    // comb_mem = row.audit_ts | col.audit_ts
+    k_u32_to_fr<<<grid_for(cells, 256), 256, 0, s>>>(audit.u(), cells, mem.u() + 8 * (size_t)rc * cells);
+    TPST_HIP(ctx, hipGetLastError());
+  }
+  k_vals_padded<<<grid_for(M3, 256), 256, 0, s>>>(R->oval[0].u(), R->oval[1].u(), R->oval[2].u(),
+                                                  (uint32_t)R->nnz[0], (uint32_t)R->nnz[1], (uint32_t)R->nnz[2], N,
+                                                  ops.u() + 8 * 4 * M3);
+  TPST_HIP(ctx, hipGetLastError());
+  TPST_HIP(ctx, hipStreamSynchronize(s));
+  return TPST_OK;
+}
+
 // R1CSInstance::commit -> SparseMatPolynomial::multi_commit over (A, B, C)
 // (r1csinstance.rs:313-344, sparse_mlpoly.rs:490-517): the SPARK dense
 // representation (row / col addresses and memory-checking timestamps, values)
@@ -807,55 +878,16 @@ extern "C" int tpst_r1cs_commit(tpst_ctx* ctx, tpst_r1cs* R, const uint8_t* labe
   while (N < maxnz) N <<= 1;
   const int vx = log2_exact(R->num_cons), vy = log2_exact(R->ncols);
   const int vmax = vx > vy ? vx : vy;
-  const size_t cells = (size_t)1 << vmax;
   const int ell_ops = log2_exact(N) + 4, ell_mem = vmax + 1;  // batch 3: (3 * 5).next_power_of_two() = 16
   const size_t L_ops = (size_t)1 << (ell_ops / 2), R_ops = (size_t)1 << (ell_ops - ell_ops / 2);
   const size_t L_mem = (size_t)1 << (ell_mem / 2), R_mem = (size_t)1 << (ell_mem - ell_mem / 2);
   *ops_rows = L_ops;
   *mem_rows = L_mem;
   if (!comm_ops || !comm_mem) return TPST_OK;  // size query
-  if (3 * N >= ((size_t)1 << 31)) return fail(ctx, TPST_E_ARG, "instance too large");
-  DevBuf ops, mem;
-  {
-    std::lock_guard<tpst::CtxMutex> lk(ctx->mu);
-    TPST_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
-    const size_t M3 = 3 * N;
-    TPST_HIP(ctx, ops.alloc(16 * N * 32));
-    TPST_HIP(ctx, mem.alloc(2 * cells * 32));
-    TPST_HIP(ctx, hipMemsetAsync(ops.p, 0, 16 * N * 32, s));
-    DevBuf addr, pos, skey, spos, rts, audit, tmp;
-    TPST_HIP(ctx, addr.alloc(M3 * 4));
-    TPST_HIP(ctx, pos.alloc(M3 * 4));
-    TPST_HIP(ctx, skey.alloc(M3 * 4));
-    TPST_HIP(ctx, spos.alloc(M3 * 4));
-    TPST_HIP(ctx, rts.alloc(M3 * 4));
-    TPST_HIP(ctx, audit.alloc(cells * 4));
-    TPST_HIP(ctx, tmp.alloc(scan_sort::sort_scratch(M3) * 4));
-    for (int rc = 0; rc < 2; rc++) {  // rows, then columns
-      const DevBuf* o = rc ? R->ocol : R->orow;
-      k_ops_addr<<<grid_for(M3, 256), 256, 0, s>>>(o[0].u(), o[1].u(), o[2].u(), (uint32_t)R->nnz[0],
-                                                   (uint32_t)R->nnz[1], (uint32_t)R->nnz[2], N, addr.u(), pos.u());
-      TPST_HIP(ctx, hipGetLastError());
-      // stable by address: equal addresses keep position order (the timestamps' rank)
-      TPST_HIP(ctx, scan_sort::stable_sort_pairs(s, addr.u(), pos.u(), skey.u(), spos.u(), M3, vmax + 1, tmp.u()));
-      TPST_HIP(ctx, hipMemsetAsync(audit.p, 0, cells * 4, s));
-      k_timestamps<<<grid_for(M3, 256), 256, 0, s>>>(skey.u(), spos.u(), M3, rts.u(), audit.u());
-      TPST_HIP(ctx, hipGetLastError());
-      // comb_ops segments: row.ops_addr | row.read_ts | col.ops_addr | col.read_ts | val | 0
-      uint32_t* base = ops.u() + 8 * (size_t)(rc * 2) * M3;
-      k_u32_to_fr<<<grid_for(M3, 256), 256, 0, s>>>(addr.u(), M3, base);
-      k_u32_to_fr<<<grid_for(M3, 256), 256, 0, s>>>(rts.u(), M3, base + 8 * M3);
-      // comb_mem = row.audit_ts | col.audit_ts
-      k_u32_to_fr<<<grid_for(cells, 256), 256, 0, s>>>(audit.u(), cells, mem.u() + 8 * (size_t)rc * cells);
-      TPST_HIP(ctx, hipGetLastError());
-    }
-    k_vals_padded<<<grid_for(M3, 256), 256, 0, s>>>(R->oval[0].u(), R->oval[1].u(), R->oval[2].u(),
-                                                    (uint32_t)R->nnz[0], (uint32_t)R->nnz[1], (uint32_t)R->nnz[2], N,
-                                                    ops.u() + 8 * 4 * M3);
-    TPST_HIP(ctx, hipGetLastError());
-    TPST_HIP(ctx, hipStreamSynchronize(s));
-  }
+  tpst_r1cs_decomm dense;
+  if (int rc = r1cs_dense_rep(ctx, R, dense)) return rc;
+  const DevBuf& ops = dense.ops;
+  const DevBuf& mem = dense.mem;
   // the two Hyrax commitments (the library calls below take the context lock)
   struct Job {
     const DevBuf* buf;

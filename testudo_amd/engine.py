@@ -114,7 +114,9 @@ class Context:
               "r1cs_eval_eq", "r1cs_eval",
               # tpst_hyrax_eval_prove: the L / R eq tables; bound; the dot-product proof (host work included)
               "hyrax_eq", "hyrax_bound", "hyrax_rounds",
-              "prodtree_build", "prodtree_rounds", "prodtree_round0", "prodtree_round1")
+              "prodtree_build", "prodtree_rounds", "prodtree_round0", "prodtree_round1",
+              # tpst_r1cs_eval_prove: k_deref; k_hash_ops; k_hash_mem; k_seg_eval (both groups, with their sums)
+              "sparse_deref", "sparse_hash_ops", "sparse_hash_mem", "sparse_seg_eval")
 
     def profile(self, on: bool):
         self.check(self.lib.tpst_profile_enable(self.h, 1 if on else 0), "tpst_profile_enable")
