@@ -734,6 +734,52 @@ int tpst_de_open_proof(const uint8_t* pst, size_t pst_len, const uint8_t* mipp, 
 int tpst_ser_committer_key(int nv, const uint64_t* srs_flat, size_t flat_len, uint8_t* out, size_t cap,
                            size_t* len);  /* flat_len == tpst_srs_flat_len(nv) */
 
+/* ---- batched point decompression and validation (csrc/point_codec.hip) ------
+ * One device lane per point, at any n: the steps of tpst_de_g1 / tpst_de_g2
+ * and of tpst_g1_check / tpst_g2_check, with the same verdict on every input.
+ * n compressed points -> n x 12 (G1) / n x 24 (G2) canonical limbs, Validate::Yes on the device.
+ * TPST_E_ARG if any point is rejected: *first_bad (may be NULL) = lowest rejected index, out is
+ * then not to be used.  n == 0 is TPST_OK. */
+int tpst_de_g1_batch(tpst_ctx* ctx, const uint8_t* in, size_t n, uint64_t* out, size_t* first_bad);
+int tpst_de_g2_batch(tpst_ctx* ctx, const uint8_t* in, size_t n, uint64_t* out, size_t* first_bad);
+/* n canonical affine points -> TPST_OK, or TPST_E_VERIFY with *first_bad */
+int tpst_g1_check_batch(tpst_ctx* ctx, const uint64_t* pts, size_t n, size_t* first_bad);
+int tpst_g2_check_batch(tpst_ctx* ctx, const uint64_t* pts, size_t n, size_t* first_bad);
+
+/* ---- arkworks wire format of the SPARK objects (csrc/serialize.hip) ---------
+ * Compress::Yes, as above.  The writers are host only; the readers walk the
+ * structure on the host (csrc/wire_spark.h) and validate all the object's
+ * points in one device batch.  Readers return TPST_E_ARG for a truncated input,
+ * trailing bytes, a length prefix other than the one the sizes imply or beyond
+ * the input or a caller capacity (checked before anything is allocated or
+ * copied), batch_size != 3, an Fr >= r, or a rejected point.
+ *
+ * R1CSCommitment { num_cons, num_vars, num_inputs, SparseMatPolyCommitment {
+ * batch_size, num_ops, num_mem_cells, comm_comb_ops: Vec<G1>, comm_comb_mem:
+ * Vec<G1> } } (r1csinstance.rs:55-61, sparse_mlpoly.rs:325-332). */
+int tpst_ser_r1cs_commitment(size_t num_cons, size_t num_vars, size_t num_inputs, size_t num_ops,
+                             size_t num_mem_cells, const uint64_t* comm_ops, size_t ops_rows,
+                             const uint64_t* comm_mem, size_t mem_rows, uint8_t* out, size_t cap, size_t* len);
+/* dims = num_cons, num_vars, num_inputs, num_ops, num_mem_cells.  With comm_ops
+ * and comm_mem NULL and both capacities 0 only dims and the row counts are
+ * reported (no point is validated). */
+int tpst_de_r1cs_commitment(tpst_ctx* ctx, const uint8_t* in, size_t len, size_t dims[5], uint64_t* comm_ops,
+                            size_t ops_cap, size_t* ops_rows, uint64_t* comm_mem, size_t mem_cap, size_t* mem_rows);
+/* R1CSEvalProof (r1csinstance.rs:336-339, sparse_mlpoly.rs:1441-1445, :1337-
+ * 1341, :1043-1050, :691-700; product_tree.rs:138-170; nizk/mod.rs:31-38) from
+ * and to the buffers of tpst_r1cs_eval_prove / _verify of these sizes. */
+int tpst_ser_r1cs_eval_proof(const tpst_r1cs_eval_sizes* sizes, const tpst_r1cs_eval_proof* proof,
+                             const uint64_t* comm_derefs, const uint64_t* prod_ops, const uint64_t* prod_mem,
+                             uint8_t* out, size_t cap, size_t* len);
+int tpst_de_r1cs_eval_proof(tpst_ctx* ctx, const uint8_t* in, size_t len, const tpst_r1cs_eval_sizes* sizes,
+                            tpst_r1cs_eval_proof* proof, uint64_t* comm_derefs, uint64_t* prod_ops,
+                            uint64_t* prod_mem);
+/* inverse of tpst_ser_committer_key: flat = the tpst_srs_export layout, so
+ * tpst_srs_load takes it.  With flat NULL and flat_cap 0 only *nv and
+ * *flat_len are reported. */
+int tpst_de_committer_key(tpst_ctx* ctx, const uint8_t* in, size_t len, int* nv, uint64_t* flat, size_t flat_cap,
+                          size_t* flat_len);
+
 /* ---- utilities ----------------------------------------------------------- */
 /* out[i] = scalars[i] * G1 generator (affine, canonical); synthetic bases */
 int tpst_g1_mul_generator(tpst_ctx* ctx, const uint64_t* scalars, size_t n, uint64_t* out);
@@ -746,7 +792,8 @@ int tpst_g1_mul_generator_dev(tpst_ctx* ctx, const void* d_scalars, size_t n, vo
  * variants (two interleaved accumulation chains / independent columns), 5 = G1 XYZZ doubling, 15 = Fq inverse
  * by a whole wave (csrc/inv_wave.h; one chain per 64 threads), 16 + op = one wave
  * running `iters` stages of wave-engine op `op` (csrc/wave_ops.inc), 13 = G1 XYZZ mixed add
- * over the radix-2^29 field, 116 = its chain-start form (ZZ = ZZZ = 1).  Runs `threads`
+ * over the radix-2^29 field, 116 = its chain-start form (ZZ = ZZZ = 1), 20 = the verifiers' host
+ * check of `threads` row commitments (up to 16 host threads; host milliseconds of one pass).  Runs `threads`
  * threads x `iters` dependent ops each; returns kernel milliseconds. */
 int tpst_microbench(tpst_ctx* ctx, int kind, size_t threads, int iters, double* ms);
 /* shader-clock cycles of the parts of `iters` stages of wave op `op` (forms,
@@ -809,7 +856,9 @@ int tpst_selftest_tower(tpst_ctx* ctx, int op, size_t n, const uint64_t* a, cons
  * between launches included); 22 / 23: round 0 / round 1 of its layer 0 alone
  * (round kernel and reduce); 24 / 25 / 26 / 27: tpst_r1cs_eval_prove's
  * k_deref / k_hash_ops / k_hash_mem / k_seg_eval (both groups, with their
- * partial sums). */
+ * partial sums); 28: the batched point decompression / validation kernels
+ * (tpst_de_g1_batch and its kin, the wire-format readers, the verifiers' row
+ * checks from POINT_CHECK_DEVICE_MIN points up). */
 int tpst_profile_enable(tpst_ctx* ctx, int on);
 int tpst_profile_reset(tpst_ctx* ctx);
 int tpst_profile_read(tpst_ctx* ctx, int stage, double* total_ms, uint64_t* launches);

@@ -158,6 +158,17 @@ PROTOTYPES = [
     ("tpst_ser_mipp_proof", C.c_int, [_vp, C.c_char_p, _sz, C.POINTER(_sz)]),
     ("tpst_de_open_proof", C.c_int, [C.c_char_p, _sz, C.c_char_p, _sz, _vp]),
     ("tpst_ser_committer_key", C.c_int, [C.c_int, _u64p, _sz, C.c_char_p, _sz, C.POINTER(_sz)]),
+    ("tpst_de_g1_batch", C.c_int, [_vp, C.c_char_p, _sz, _u64p, C.POINTER(_sz)]),
+    ("tpst_de_g2_batch", C.c_int, [_vp, C.c_char_p, _sz, _u64p, C.POINTER(_sz)]),
+    ("tpst_g1_check_batch", C.c_int, [_vp, _u64p, _sz, C.POINTER(_sz)]),
+    ("tpst_g2_check_batch", C.c_int, [_vp, _u64p, _sz, C.POINTER(_sz)]),
+    ("tpst_ser_r1cs_commitment", C.c_int, [_sz, _sz, _sz, _sz, _sz, _u64p, _sz, _u64p, _sz, C.c_char_p, _sz,
+                                           C.POINTER(_sz)]),
+    ("tpst_de_r1cs_commitment", C.c_int, [_vp, C.c_char_p, _sz, C.POINTER(_sz), _u64p, _sz, C.POINTER(_sz), _u64p,
+                                          _sz, C.POINTER(_sz)]),
+    ("tpst_ser_r1cs_eval_proof", C.c_int, [_vp, _vp, _u64p, _u64p, _u64p, C.c_char_p, _sz, C.POINTER(_sz)]),
+    ("tpst_de_r1cs_eval_proof", C.c_int, [_vp, C.c_char_p, _sz, _vp, _vp, _u64p, _u64p, _u64p]),
+    ("tpst_de_committer_key", C.c_int, [_vp, C.c_char_p, _sz, C.POINTER(C.c_int), _u64p, _sz, C.POINTER(_sz)]),
     ("tpst_profile_enable", C.c_int, [_vp, C.c_int]),
     ("tpst_profile_reset", C.c_int, [_vp]),
     ("tpst_profile_read", C.c_int, [_vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),

@@ -27,6 +27,7 @@
 #include "device_util.h"
 #include "fr_sponge.h"
 #include "gens_state.h"
+#include "point_codec.h"
 #include "pst_kernels.h"
 #include "pst_state.h"
 
@@ -642,11 +643,8 @@ extern "C" int tpst_hyrax_eval_verify(tpst_ctx* ctx, const tpst_gens* g, const u
   const size_t Ls = (size_t)1 << lv, Rs = (size_t)1 << rv;
   // element checks before the transcript absorbs anything
   bool ok = proof_elements_ok(proof, rv) && point_valid<Fq>(C_Zr);
-  if (ok) {
-    std::vector<char> bad(Ls, 0);
-    host::parallel_for(Ls, [&](size_t i) { bad[i] = !point_valid<Fq>(comm + 12 * i); });
-    for (size_t i = 0; i < Ls; i++) ok = ok && !bad[i];
-  }
+  if (ok)  // the host loop below POINT_CHECK_DEVICE_MIN rows, the device check from there
+    if (int rc = g1_rows_valid(ctx, comm, Ls, &ok)) return rc;
   if (!ok) return fail(ctx, TPST_E_VERIFY, "malformed proof element or commitment");
   // L, R by the eq-table kernel; C_LZ = MSM(comm, L) by the variable-base MSM
   // (library calls: each takes the context lock itself)

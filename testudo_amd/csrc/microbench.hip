@@ -8,6 +8,7 @@
 #include "rns_engine.h"
 #include "field29.h"
 #include "inv_wave.h"
+#include "point_codec.h"
 
 using namespace tpst;
 
@@ -458,6 +459,7 @@ extern "C" int tpst_microbench_wave_phases(tpst_ctx* ctx, int op, int iters, uin
 
 extern "C" int tpst_microbench(tpst_ctx* ctx, int kind, size_t threads, int iters, double* ms) {
   if (!ctx || !ms || threads == 0 || iters <= 0) return fail(ctx, TPST_E_ARG, "bad argument");
+  if (kind == 20) return tpst::g1_rows_host_bench(ctx, threads, iters, ms);  // host work: takes no lock here
   std::lock_guard<tpst::CtxMutex> lk(ctx->mu);
   TPST_HIP(ctx, hipSetDevice(ctx->device));
   const bool rnsk = kind >= 64 && kind < 96;

@@ -52,6 +52,8 @@ enum MsmStage {
   // tpst_r1cs_eval_prove: the memory dereference; the hash layer over the ops and over the cells; the segmented
   // multi-evaluation (both groups, partial sums included)
   ST_SPARSE_DEREF, ST_SPARSE_HASH_OPS, ST_SPARSE_HASH_MEM, ST_SPARSE_SEG_EVAL,
+  // point_codec.hip: batched point decompression / validation (one launch per batch)
+  ST_POINT_CODEC,
   N_STAGES
 };
 

@@ -2,7 +2,9 @@
 // objects: Commitment, Proof, MippProof (mipp.rs:21-28, derive
 // CanonicalSerialize), CommitterKey -- the byte strings whose lengths are the
 // proof_size / commiter_key_size columns of benches/pst.rs:43-46,64-74.
-// Host-only code (no device work): the proof is a few KB.
+// Host-only code (no device work): the proof is a few KB.  The SPARK objects
+// at the end of this file (R1CSCommitment, R1CSEvalProof) and the CommitterKey
+// reader hold thousands of points: their readers validate on the device.
 //
 // Restated encoding rules (ark-serialize / ark-ff / ark-ec 0.4):
 //  * Fp: canonical value, little-endian, buffer_byte_size(MODULUS_BIT_SIZE +
@@ -23,7 +25,10 @@
 #include <vector>
 
 #include "../../include/tpst.h"
+#include "ctx.h"
 #include "curve.h"
+#include "point_codec.h"
+#include "wire_spark.h"
 
 using namespace tpst;
 
@@ -434,4 +439,203 @@ extern "C" int tpst_ser_committer_key(int nv, const uint64_t* flat, size_t flat_
   w.point<Fq>(g);
   w.point<Fq2>(h);
   return finish(w, len);
+}
+
+// ======================================================== SPARK objects ==
+// R1CSCommitment, R1CSEvalProof and the reader of CommitterKey.  The layouts
+// are the item lists of wire_spark.h (restated there from r1csinstance.rs:
+// 55-61, 336-339, sparse_mlpoly.rs:52-55, 84-87, 325-332, 691-700, 1043-1050,
+// 1337-1341, 1441-1445, product_tree.rs:138-170, sumcheck.rs:19-22,
+// unipoly.rs:7-11, nizk/mod.rs:31-38, nizk/bullet.rs:19-23).  The writers are
+// host only.  The readers walk the structure on the host, range-check every Fr,
+// then hand all the object's points to the device in one batch per group
+// (point_codec.hip): these objects hold thousands of points.
+namespace {
+
+bool lt_r(const uint64_t* a) {  // a < r (canonical Fr)
+  for (int i = 3; i >= 0; i--) {
+    const uint64_t ri = (uint64_t)params::FR_P[2 * i] | ((uint64_t)params::FR_P[2 * i + 1] << 32);
+    if (a[i] != ri) return a[i] < ri;
+  }
+  return false;
+}
+
+// a G1 point of these objects: canonical and on the curve (one product chain; the subgroup is the
+// reader's to check), or the writer reports TPST_E_ARG
+void put_g1_checked(Writer& w, const uint64_t* p) {
+  w.point<Fq>(p);
+  if (w.ok && !on_curve(G1A{fq_in(p), fq_in(p + 6)})) w.ok = false;
+}
+
+// the rounds fields of the three openings, as the sizes fix them
+void set_rounds(const tpst_r1cs_eval_sizes& z, tpst_r1cs_eval_proof* p) {
+  p->proof_ops.rounds = wire::open_rounds(z.ell_ops);
+  p->proof_mem.rounds = wire::open_rounds(z.ell_mem);
+  p->proof_derefs.rounds = wire::open_rounds(z.ell_derefs);
+}
+bool rounds_ok(const tpst_r1cs_eval_sizes& z, const tpst_r1cs_eval_proof* p) {
+  return p->proof_ops.rounds == wire::open_rounds(z.ell_ops) && p->proof_mem.rounds == wire::open_rounds(z.ell_mem) &&
+         p->proof_derefs.rounds == wire::open_rounds(z.ell_derefs);
+}
+
+void write_items(Writer& w, const std::vector<wire::Item>& items, const uint64_t* const* bufs) {
+  for (const wire::Item& it : items) {
+    if (it.kind == wire::LEN) {
+      w.u64((uint64_t)it.count);
+      continue;
+    }
+    const uint64_t* src = bufs[it.buf] + it.word;
+    for (size_t j = 0; j < it.count; j++) {
+      if (it.kind == wire::FR) {
+        if (!lt_r(src + 4 * j)) w.ok = false;
+        w.bytes(src + 4 * j, 32);
+      } else if (it.kind == wire::G1) {
+        put_g1_checked(w, src + 12 * j);
+      } else {
+        w.point<Fq2>(src + 24 * j);
+      }
+    }
+  }
+}
+
+// the elements of a walked input into the caller's buffers: every Fr range-checked and copied, every
+// point of `kind` decompressed and validated in one device batch.  TPST_E_ARG on any rejection.
+int read_items(tpst_ctx* ctx, const uint8_t* in, const std::vector<wire::Item>& items, const std::vector<size_t>& offs,
+               uint64_t* const* bufs) {
+  for (size_t i = 0; i < items.size(); i++) {
+    const wire::Item& it = items[i];
+    if (it.kind != wire::FR) continue;
+    uint64_t* dst = bufs[it.buf] + it.word;
+    memcpy(dst, in + offs[i], it.count * 32);
+    for (size_t j = 0; j < it.count; j++)
+      if (!lt_r(dst + 4 * j)) return fail(ctx, TPST_E_ARG, "wire format: scalar >= r");
+  }
+  for (wire::Kind kind : {wire::G1, wire::G2}) {
+    const size_t B = wire::KIND_BYTES[kind], W = wire::KIND_WORDS[kind];
+    size_t n = 0;
+    for (const wire::Item& it : items)
+      if (it.kind == kind) n += it.count;
+    if (!n) continue;
+    std::vector<uint8_t> packed(n * B);  // n is bounded by the input's length: the walk placed every run
+    std::vector<uint64_t> limbs(n * W);
+    size_t k = 0;
+    for (size_t i = 0; i < items.size(); i++)
+      if (items[i].kind == kind) {
+        memcpy(&packed[k * B], in + offs[i], items[i].count * B);
+        k += items[i].count;
+      }
+    size_t bad = n;
+    const int rc = kind == wire::G1 ? point_decompress_batch<Fq>(ctx, packed.data(), n, limbs.data(), &bad)
+                                    : point_decompress_batch<Fq2>(ctx, packed.data(), n, limbs.data(), &bad);
+    if (rc) return rc;
+    if (bad != n) return fail(ctx, TPST_E_ARG, "wire format: invalid point encoding");
+    k = 0;
+    for (const wire::Item& it : items)
+      if (it.kind == kind) {
+        memcpy(bufs[it.buf] + it.word, &limbs[k * W], it.count * W * 8);
+        k += it.count;
+      }
+  }
+  return TPST_OK;
+}
+
+}  // namespace
+
+extern "C" int tpst_ser_r1cs_commitment(size_t num_cons, size_t num_vars, size_t num_inputs, size_t num_ops,
+                                        size_t num_mem_cells, const uint64_t* comm_ops, size_t ops_rows,
+                                        const uint64_t* comm_mem, size_t mem_rows, uint8_t* out, size_t cap,
+                                        size_t* len) {
+  size_t want_ops, want_mem;
+  if (!comm_ops || !comm_mem || !wire::commitment_rows(num_ops, num_mem_cells, &want_ops, &want_mem) ||
+      ops_rows != want_ops || mem_rows != want_mem)
+    return TPST_E_ARG;
+  Writer w{out, cap};
+  for (size_t v : {num_cons, num_vars, num_inputs, wire::BATCH_SIZE, num_ops, num_mem_cells}) w.u64((uint64_t)v);
+  w.u64((uint64_t)ops_rows);
+  for (size_t i = 0; i < ops_rows; i++) put_g1_checked(w, comm_ops + 12 * i);
+  w.u64((uint64_t)mem_rows);
+  for (size_t i = 0; i < mem_rows; i++) put_g1_checked(w, comm_mem + 12 * i);
+  return finish(w, len);
+}
+
+extern "C" int tpst_de_r1cs_commitment(tpst_ctx* ctx, const uint8_t* in, size_t len, size_t dims[5],
+                                       uint64_t* comm_ops, size_t ops_cap, size_t* ops_rows, uint64_t* comm_mem,
+                                       size_t mem_cap, size_t* mem_rows) {
+  if (!ctx || !in || !dims || !ops_rows || !mem_rows) return fail(ctx, TPST_E_ARG, "null argument");
+  wire::CommitmentWalk w;
+  if (!wire::walk_commitment(in, len, w)) return fail(ctx, TPST_E_ARG, "wire format: malformed R1CSCommitment");
+  for (int k = 0; k < 5; k++) dims[k] = (size_t)w.dims[k];
+  *ops_rows = w.ops_rows;
+  *mem_rows = w.mem_rows;
+  if (!comm_ops && !comm_mem && !ops_cap && !mem_cap) return TPST_OK;  // dimensions only
+  if (!comm_ops || !comm_mem) return fail(ctx, TPST_E_ARG, "null argument");
+  if (w.ops_rows > ops_cap || w.mem_rows > mem_cap) return fail(ctx, TPST_E_ARG, "wire format: capacity too small");
+  const std::vector<wire::Item> items = {{wire::G1, 0, w.ops_rows, 0}, {wire::G1, 1, w.mem_rows, 0}};
+  const std::vector<size_t> offs = {w.ops_off, w.mem_off};
+  uint64_t* const bufs[2] = {comm_ops, comm_mem};
+  return read_items(ctx, in, items, offs, bufs);
+}
+
+extern "C" int tpst_ser_r1cs_eval_proof(const tpst_r1cs_eval_sizes* sizes, const tpst_r1cs_eval_proof* proof,
+                                        const uint64_t* comm_derefs, const uint64_t* prod_ops,
+                                        const uint64_t* prod_mem, uint8_t* out, size_t cap, size_t* len) {
+  std::vector<wire::Item> items;
+  if (!sizes || !proof || !comm_derefs || !prod_ops || !prod_mem || !wire::proof_items(*sizes, items) ||
+      !rounds_ok(*sizes, proof))
+    return TPST_E_ARG;
+  const uint64_t* const bufs[4] = {reinterpret_cast<const uint64_t*>(proof), comm_derefs, prod_ops, prod_mem};
+  Writer w{out, cap};
+  write_items(w, items, bufs);
+  return finish(w, len);
+}
+
+extern "C" int tpst_de_r1cs_eval_proof(tpst_ctx* ctx, const uint8_t* in, size_t len, const tpst_r1cs_eval_sizes* sizes,
+                                       tpst_r1cs_eval_proof* proof, uint64_t* comm_derefs, uint64_t* prod_ops,
+                                       uint64_t* prod_mem) {
+  if (!ctx || !in || !sizes || !proof || !comm_derefs || !prod_ops || !prod_mem)
+    return fail(ctx, TPST_E_ARG, "null argument");
+  std::vector<wire::Item> items;
+  std::vector<size_t> offs;
+  if (!wire::proof_items(*sizes, items)) return fail(ctx, TPST_E_ARG, "wire format: sizes no proof has");
+  if (!wire::walk_items(in, len, items, offs)) return fail(ctx, TPST_E_ARG, "wire format: malformed R1CSEvalProof");
+  memset(proof, 0, sizeof(*proof));
+  set_rounds(*sizes, proof);
+  uint64_t* const bufs[4] = {reinterpret_cast<uint64_t*>(proof), comm_derefs, prod_ops, prod_mem};
+  return read_items(ctx, in, items, offs, bufs);
+}
+
+extern "C" int tpst_de_committer_key(tpst_ctx* ctx, const uint8_t* in, size_t len, int* nv, uint64_t* flat,
+                                     size_t flat_cap, size_t* flat_len) {
+  if (!ctx || !in || !nv || !flat_len) return fail(ctx, TPST_E_ARG, "null argument");
+  std::vector<wire::Item> items;
+  std::vector<size_t> offs;
+  if (!wire::walk_committer_key(in, len, nv, items, offs))
+    return fail(ctx, TPST_E_ARG, "wire format: malformed CommitterKey");
+  const int n = *nv;
+  *flat_len = tpst_srs_flat_len(n);
+  if (!flat && !flat_cap) return TPST_OK;  // dimensions only
+  if (!flat) return fail(ctx, TPST_E_ARG, "null argument");
+  if (*flat_len > flat_cap) return fail(ctx, TPST_E_ARG, "wire format: capacity too small");
+  uint64_t* const bufs[1] = {flat};
+  if (int rc = read_items(ctx, in, items, offs, bufs)) return rc;
+  // the flat SRS ends with the verifier's masks g^{t_i}, h^{t_i}, which the key does not carry:
+  // powers_of_g[i][x] = g^{eq(t[i..], x)} with t_i on x's lowest bit, so g^{t_i} is the sum of
+  // level i's odd entries (eq sums to 1 over the other variables)
+  size_t off = 36;
+  uint64_t* gmask = flat + *flat_len - (size_t)n * 36;
+  uint64_t* hmask = gmask + (size_t)n * 12;
+  std::vector<uint64_t> odd, ones;
+  for (int i = 0; i < n; i++) {
+    const size_t h = (size_t)1 << (n - i - 1);
+    ones.assign(4 * h, 0);
+    for (size_t x = 0; x < h; x++) ones[4 * x] = 1;
+    odd.resize(24 * h);
+    for (size_t x = 0; x < h; x++) memcpy(&odd[12 * x], flat + off + 12 * (2 * x + 1), 96);
+    if (int rc = tpst_g1_msm(ctx, odd.data(), h, ones.data(), h, gmask + 12 * i)) return rc;
+    off += 2 * h * 12;
+    for (size_t x = 0; x < h; x++) memcpy(&odd[24 * x], flat + off + 24 * (2 * x + 1), 192);
+    if (int rc = tpst_g2_msm(ctx, odd.data(), h, ones.data(), h, hmask + 24 * i)) return rc;
+    off += 2 * h * 24;
+  }
+  return TPST_OK;
 }

@@ -35,6 +35,7 @@
 #include "ctx.h"
 #include "device_util.h"
 #include "fr_sponge.h"
+#include "point_codec.h"
 #include "product_tree.h"
 #include "pst_kernels.h"
 #include "r1cs_state.h"
@@ -381,12 +382,11 @@ bool dotprod_elements_ok(const tpst_dotprod_proof* pr, int lg) {
   return true;
 }
 
-bool points_ok(const uint64_t* p, size_t n) {
-  std::vector<char> bad(n, 0);
-  host::parallel_for(n, [&](size_t i) { bad[i] = !point_valid<Fq>(p + 12 * i); });
-  for (size_t i = 0; i < n; i++)
-    if (bad[i]) return false;
-  return true;
+// ok = ok && every row commitment is valid: g1_rows_valid (point_codec.h) runs the host loop below
+// POINT_CHECK_DEVICE_MIN rows and the device check from there
+int points_ok(tpst_ctx* ctx, const uint64_t* p, size_t n, bool& ok) {
+  if (!ok) return TPST_OK;
+  return g1_rows_valid(ctx, p, n, &ok);
 }
 
 // hash(addr, val, ts) - gamma (sparse_mlpoly.rs:559), Montgomery
@@ -674,7 +674,9 @@ extern "C" int tpst_r1cs_eval_verify(tpst_ctx* ctx, const uint64_t* comm_ops, co
             frs_ok(prod_mem, len_mem);
   ok = ok && dotprod_elements_ok(&pf->proof_derefs, d.lg_cols(2)) && dotprod_elements_ok(&pf->proof_ops, d.lg_cols(0)) &&
        dotprod_elements_ok(&pf->proof_mem, d.lg_cols(1));
-  ok = ok && points_ok(comm_derefs, d.rows(2)) && points_ok(comm_ops, d.rows(0)) && points_ok(comm_mem, d.rows(1));
+  if (int rc = points_ok(ctx, comm_derefs, d.rows(2), ok)) return rc;
+  if (int rc = points_ok(ctx, comm_ops, d.rows(0), ok)) return rc;
+  if (int rc = points_ok(ctx, comm_mem, d.rows(1), ok)) return rc;
   if (!ok) return fail(ctx, TPST_E_VERIFY, "malformed proof element, commitment or argument");
   const auto bad = [&](const char* what) { return fail(ctx, TPST_E_VERIFY, what); };
   for (size_t i = 0; i < d.rows(2); i++) tr.point(comm_derefs + 12 * i);

@@ -116,7 +116,9 @@ class Context:
               "hyrax_eq", "hyrax_bound", "hyrax_rounds",
               "prodtree_build", "prodtree_rounds", "prodtree_round0", "prodtree_round1",
               # tpst_r1cs_eval_prove: k_deref; k_hash_ops; k_hash_mem; k_seg_eval (both groups, with their sums)
-              "sparse_deref", "sparse_hash_ops", "sparse_hash_mem", "sparse_seg_eval")
+              "sparse_deref", "sparse_hash_ops", "sparse_hash_mem", "sparse_seg_eval",
+              # point_codec.hip: batched point decompression / validation
+              "point_codec")
 
     def profile(self, on: bool):
         self.check(self.lib.tpst_profile_enable(self.h, 1 if on else 0), "tpst_profile_enable")

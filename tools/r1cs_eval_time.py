@@ -16,6 +16,13 @@ from a resident decommitment and after one warm-up of every call, medians over
                         k_hash_mem  2 cells (32 + 4 B read) + 4 cells 32 B written
                         k_seg_eval  (21 + 1) N 32 B + (2 + 1) cells 32 B read
                       (seg_eval covers both groups and their partial sums)
+  verify_rows_host16_once_ms   the verifier's row-commitment validation alone, the way the host
+                      does it (tpst_microbench kind 20: host::parallel_for over point_valid, up to
+                      16 threads) over as many points as comm_derefs, comm_ops and comm_mem hold,
+                      one pass (the verifier makes two)
+  verify_point_codec_dev_ms / _launches   the device row checks of one verify (point_codec stage)
+  proof_bytes / commitment_bytes   the arkworks wire format (Compress::Yes) of the proof and of the
+                      commitment it opens, as the library's writers give them
   host_transcript_ms  the prover's absorbs and squeezes replayed alone on the host
   parts_wall_ms       what could be timed before this call existed, on
                       same-shaped inputs: three tpst_hyrax_eval_prove_dev (ell =
@@ -27,6 +34,7 @@ from a resident decommitment and after one warm-up of every call, medians over
 Prints one JSON line per size.
 """
 import argparse
+import ctypes as C
 import json
 import os
 import statistics
@@ -98,6 +106,7 @@ def main():
 
     from testudo_amd import Context
     from testudo_amd import product_tree as PT
+    from testudo_amd import serialize as W
     from testudo_amd.hyrax import FrTranscript, HyraxGens, eval_prove
     from testudo_amd.r1cs import R1CSInstance
     from testudo_amd.r1cs_eval import R1CSCommitmentGens, R1CSEvalProof, commit_decomm
@@ -148,6 +157,23 @@ def main():
             vwall.append((time.perf_counter() - t0) * 1e3)
             assert ok
             thost.append(replay_transcript(sz, FrTranscript, one, comm.comm_mem[0]))
+        vcodec = []  # the device row checks, in runs of their own (stage events stay out of the wall time)
+        ctx.profile(True)
+        for _ in range(args.runs):
+            ctx.profile_reset()
+            assert proof.verify(comm, rx, ry, evals, gens, FrTranscript())
+            vcodec.append(ctx.profile_read()["point_codec"])
+        ctx.profile(False)
+        # the verifier's row-commitment validation alone, as the host does it below the device
+        # threshold, over as many points as comm_derefs, comm_ops and comm_mem hold, once
+        # (the verifier checks every row twice: in its own element checks and in each opening's)
+        n_rows = len(proof.comm_derefs) + len(comm.comm_ops) + len(comm.comm_mem)
+        rows_host = []
+        for _ in range(args.runs + 1):
+            ms = C.c_double(0)
+            assert ctx.lib.tpst_microbench(ctx.h, 20, n_rows, 1, C.byref(ms)) == 0
+            rows_host.append(ms.value)
+        rows_host = rows_host[1:]
 
         # ---- the parts the parent could already time, on same-shaped inputs
         def dev_fr(count, seed):
@@ -184,7 +210,12 @@ def main():
         res = {"log_cons": lg, "num_ops": N, "num_mem_cells": cells, "runs": args.runs,
                "prove_wall_ms": round(med(wall), 3), "verify_wall_ms": round(med(vwall), 3),
                "host_transcript_ms": round(med(thost), 3), "parts_wall_ms": round(med(parts), 3),
-               "assembly_ms": round(med(wall) - med(parts), 3)}
+               "assembly_ms": round(med(wall) - med(parts), 3),
+               "proof_bytes": len(W.ser_r1cs_eval_proof(proof, sz)),
+               "commitment_bytes": len(W.ser_r1cs_commitment(comm, n, n, 10)),
+               "verify_rows": n_rows, "verify_rows_host16_once_ms": round(med(rows_host), 3),
+               "verify_point_codec_dev_ms": round(med([v[0] for v in vcodec]), 3),
+               "verify_point_codec_launches": int(med([v[1] for v in vcodec]))}
         for s, ms in dev_ms.items():
             gbs = nbytes[s] / (med(ms) * 1e-3) / 1e9 if med(ms) > 0 else 0.0
             res[s] = {"dev_ms": round(med(ms), 4), "bytes": nbytes[s], "gbs": round(gbs, 1),
