@@ -24,7 +24,7 @@ __device__ __forceinline__ Affine<Fq29> rec29_point(const uint32_t* w, uint32_t 
 }
 
 __device__ __forceinline__ Affine<Fq29> fetch_rec29(const uint32_t* table, uint32_t v) {
-  const uint4* r = reinterpret_cast<const uint4*>(table + (size_t)(v & 0x7fffffffu) * REC29_WORDS);
+  const uint4* r = reinterpret_cast<const uint4*>(table + (size_t)(v & VAL_INDEX) * REC29_WORDS);
   uint32_t w[28];
 #pragma unroll
   for (int i = 0; i < 7; i++) {
@@ -65,7 +65,7 @@ __device__ __forceinline__ void stage_read(const uint4 (*buf)[ACC_BLOCK], int la
 template <class F>
 __device__ __forceinline__ Affine<F> fetch_point(const uint32_t* bases, const uint32_t* phib, uint32_t nbase,
                                                 uint32_t v) {
-  const uint32_t idx = v & 0x7fffffffu;
+  const uint32_t idx = v & VAL_INDEX;
   Affine<F> p = (idx < nbase) ? load_affine<F>(bases, idx) : load_affine<F>(phib, idx - nbase);
   if (v >> 31) p.y = neg(p.y);
   return p;
@@ -219,7 +219,10 @@ __global__ void __launch_bounds__(64, (sizeof(F) > 48 ? 1 : 2))
 // sums them per bucket.  One launch covers the entries of windows [wlo, whi)
 // (range[w] = first sorted entry of window w, device-side): chunk indices stay
 // global (t = entry >> lg) so a chunk straddling two window groups is split
-// between their launches without sharing a part[] slot.
+// between their launches without sharing a part[] slot.  The G1 kernels
+// (this one and k_bucket_acc_short_lds) walk by the first / last flags of the
+// sorted values and never read bstart / bend; keys only for a bucket stored
+// whole.  The G2 pair kernel keeps the walk by keys and bounds.
 template <class F, int MINW = (sizeof(F) > 48 ? 1 : 2), bool REC29 = false>
 __global__ void __launch_bounds__(64, MINW)
     k_bucket_acc_short(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
@@ -241,30 +244,35 @@ __global__ void __launch_bounds__(64, MINW)
     else
       return A::in(fetch_point<F>(bases, phib, nbase, v));
   };
+  // the walk of k_bucket_acc_short_lds below, the next point prefetched into
+  // registers: val_n was loaded one step ago, the load issued here is vals[e + 2]
+  const size_t steps = c1 - c0;
+  if (steps == 0) return;  // an empty window group
   uint32_t key = keys[c0];
-  Affine<C> pt;
-  if (key < sent) pt = fetch(vals[c0]);
+  uint32_t val = vals[c0];
+  uint32_t val_n = steps > 1 ? vals[c0 + 1] : 0u;
+  uint32_t first_val = val;
+  Affine<C> pt = fetch(val);
   Xyzz<C> acc = Xyzz<C>::inf();
-  int step = 0;  // the same in every lane still in the loop
-  for (size_t e = c0; e < c1; e++, step++) {
-    uint32_t key_n = sent;
+  for (size_t s = 0; s < steps; s++) {  // s is the same in every lane still in the loop
+    const size_t e = c0 + s;
+    const uint32_t val_nn = s + 2 < steps ? vals[e + 2] : 0u;
+    const uint32_t first_n = run_ends(val, s + 1 == steps) ? val_n : first_val;
+    const uint32_t key_n = s + 1 < steps && run_slot(first_n, val_n) == RUN_BUCKET ? keys[e + 1] : 0u;
     Affine<C> pt_n;
-    if (e + 1 < c1) {
-      key_n = keys[e + 1];
-      if (key_n < sent) pt_n = fetch(vals[e + 1]);
+    if (s + 1 < steps) pt_n = fetch(val_n);
+    acc = add_affine(acc, pt, TPST_CHAIN_UNIT && s == 1);
+    if (run_ends(val, s + 1 == steps)) {
+      const uint32_t slot = run_slot(first_val, val);
+      if (slot == RUN_BUCKET)
+        store_pk(buckets, key, acc);
+      else
+        store_pk(part, 2 * t + slot, acc);
+      acc = Xyzz<C>::inf();
     }
-    if (key < sent) {
-      acc = add_affine(acc, pt, TPST_CHAIN_UNIT && step == 1);
-      if (key_n != key) {
-        const bool starts = bstart[key] >= c0;
-        const bool ends = bend[key] <= c1;
-        if (starts && ends)
-          store_pk(buckets, key, acc);
-        else
-          store_pk(part, 2 * t + (starts ? 1 : 0), acc);
-        acc = Xyzz<C>::inf();
-      }
-    }
+    val = val_n;
+    val_n = val_nn;
+    first_val = first_n;
     key = key_n;
     pt = pt_n;
   }
@@ -305,7 +313,7 @@ __global__ void __launch_bounds__(64, MINW)
   // every lane issues every staging load (the instruction is wave-wide);
   // lanes without a point load bases[0]
   auto load_next = [&](int buf, uint32_t v, bool want) {
-    const uint32_t idx = v & 0x7fffffffu;
+    const uint32_t idx = v & VAL_INDEX;
     stage_load<NP>(stage[buf], !want  ? bases
                                : REC29 ? bases + (size_t)REC29_WORDS * idx
                                        : ((idx < nbase) ? bases + 24 * (size_t)idx : phib + 24 * (size_t)(idx - nbase)));
@@ -321,36 +329,56 @@ __global__ void __launch_bounds__(64, MINW)
       return A::in(p);
     }
   };
-  uint32_t key = active ? keys[c0] : sent;
-  uint32_t val = active && key < sent ? vals[c0] : 0u;
-  load_next(0, val, key < sent);
+  // The walk reads nothing but vals[]: every entry of [c0, c1) is live (zero
+  // digits sort past range[W]) and its flags say where its bucket starts and
+  // ends (msm_pieces.h run_ends / run_slot).  No load is consumed in the step
+  // that issues it: the value two entries ahead is issued after the step's
+  // wait for the staged point and first used one step later, behind the next
+  // wait, so the mixed add covers its latency and a bucket's end waits for
+  // nothing.  Only a bucket lying wholly inside the chunk needs its key: the
+  // flags of the entry ahead tell one step early, and the key is loaded then.
+  const size_t steps = c1 - c0;  // per lane (0: no chunk, or an empty window group)
+  // (the first key unconditionally and ahead of the values: the wait for them
+  // covers it, so the compiler carries no pending load into the loop)
+  uint32_t key = steps > 0 ? keys[c0] : 0u;
+  uint32_t val = steps > 0 ? vals[c0] : 0u;
+  uint32_t val_n = steps > 1 ? vals[c0 + 1] : 0u;
+  uint32_t first_val = val;  // first entry of the current run
+  // Stores count on vmcnt like loads and complete in order with them, so the
+  // wait for a staged point would also wait for a run's stores issued just
+  // before it (some lane of a wave ends a run in almost every step).  The
+  // next point is therefore read back at the end of the step, after the add
+  // and before the step's stores: the wait then finds this step's loads, a
+  // whole add old, and the stores get the next add to complete (a small part
+  // of the measured stall: profiles/acc_loop).
+  load_next(0, val, steps > 0);
   Xyzz<C> acc = Xyzz<C>::inf();
-  const size_t steps = c1 - c0;  // per lane; the loop runs to the wave's longest chunk
-  const size_t maxsteps = (size_t)1 << lg;
+  Affine<C> pt = read_point(0, val);
+  const size_t maxsteps = (size_t)1 << lg;  // the loop runs to the wave's longest chunk
   for (size_t s = 0; s < maxsteps; s++) {
     const size_t e = c0 + s;
-    const bool live = s < steps;
-    uint32_t key_n = sent, val_n = 0;
-    if (s + 1 < steps) {
-      key_n = keys[e + 1];
-      if (key_n < sent) val_n = vals[e + 1];
+    uint32_t val_nn = s + 2 < steps ? vals[e + 2] : 0u;
+    // the run entry e + 1 belongs to; its key when it ends there as a whole bucket
+    const uint32_t first_n = run_ends(val, s + 1 == steps) ? val_n : first_val;
+    uint32_t key_n = s + 1 < steps && run_slot(first_n, val_n) == RUN_BUCKET ? keys[e + 1] : 0u;
+    load_next((int)((s + 1) & 1), val_n, s + 1 < steps);
+    if (s < steps) acc = add_affine(acc, pt, TPST_CHAIN_UNIT && s == 1);
+    pt = read_point((int)((s + 1) & 1), val_n);
+    // the loaded words are complete here: the compiler places its own wait for
+    // them at this point and none behind the stores
+    asm volatile("" : "+v"(val_nn), "+v"(key_n));
+    if (s < steps && run_ends(val, s + 1 == steps)) {
+      const uint32_t slot = run_slot(first_val, val);
+      if (slot == RUN_BUCKET)
+        store_pk(buckets, key, acc);
+      else
+        store_pk(part, 2 * t + slot, acc);
+      acc = Xyzz<C>::inf();
     }
-    const Affine<C> pt = read_point((int)(s & 1), val);
-    load_next((int)((s + 1) & 1), val_n, key_n < sent);
-    if (live && key < sent) {
-      acc = add_affine(acc, pt, TPST_CHAIN_UNIT && s == 1);
-      if (key_n != key) {
-        const bool starts = bstart[key] >= c0;
-        const bool ends = bend[key] <= c1;
-        if (starts && ends)
-          store_pk(buckets, key, acc);
-        else
-          store_pk(part, 2 * t + (starts ? 1 : 0), acc);
-        acc = Xyzz<C>::inf();
-      }
-    }
-    key = key_n;
     val = val_n;
+    val_n = val_nn;
+    first_val = first_n;
+    key = key_n;
     if (__all(s + 1 >= steps ? 1 : 0)) break;  // wave-uniform exit
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no staging load outstanding at exit
@@ -361,7 +389,7 @@ __global__ void __launch_bounds__(64, MINW)
 // coordinate of every Fq2 value; same chunking, parking and bucket stores.
 static __device__ __forceinline__ Affine<Fq2P> fetch_point_pair(const uint32_t* bases, const uint32_t* phib, uint32_t nbase,
                                                         uint32_t v) {
-  const uint32_t idx = v & 0x7fffffffu;
+  const uint32_t idx = v & VAL_INDEX;
   Affine<Fq2P> p = (idx < nbase) ? load_affine_pair(bases, idx) : load_affine_pair(phib, idx - nbase);
   if (v >> 31) p.y = neg(p.y);
   return p;

@@ -1,6 +1,7 @@
 // Scalar decomposition and the two-pass bucket sort of the variable-base MSM.
 #pragma once
 #include "msm_common.h"
+#include "msm_pieces.h"
 
 namespace tpst {
 
@@ -41,7 +42,9 @@ __device__ __forceinline__ void load_scalar(const uint32_t* p, uint32_t* s) {
 //    range inside every bin and the bin starts;
 //  * k_sort_scatter moves each tile's entries to its slots of their bins;
 //  * k_sort_bin sorts one bin by the low lo key bits in LDS and writes the
-//    entries in key order, the bucket bounds [bstart, bend), zeroes (=
+//    entries in key order -- each value with the flags of the first and the
+//    last entry of its bucket (msm_pieces.h entry_flags), which the G1
+//    accumulation walks by --, the bucket bounds [bstart, bend), zeroes (=
 //    infinity) the buckets without entries and the window starts range[w].
 // Entries of one bucket land in an unspecified order: the bucket sum is a
 // group element, so the MSM result does not depend on it.
@@ -373,7 +376,9 @@ static __global__ void __launch_bounds__(SORT_THREADS)
 
 // one bin: counting sort by the low lo key bits.  A bin of <= SORTB_CAP
 // entries is staged in registers + LDS and written out contiguously; a larger
-// one (skewed digits) scatters straight to its slots.
+// one (skewed digits) scatters straight to its slots.  Either way an entry's
+// rank inside its bucket and the bucket's count follow from the offsets off[]
+// and give its flags.
 static __global__ void __launch_bounds__(SORTB_THREADS)
     k_sort_bin(const uint32_t* __restrict__ keys2, const uint32_t* __restrict__ vals2,
                const uint32_t* __restrict__ start, int lo, uint32_t sent, uint32_t nb, int W,
@@ -475,16 +480,19 @@ static __global__ void __launch_bounds__(SORTB_THREADS)
         else
           z = mid;
       }
+      const uint32_t b0 = off[a - 1], b1 = a < D ? off[a] : nz;  // the bucket's slots
       keys[s + p] = (b << lo) | (a - 1);
-      vals[s + p] = sval[p];
+      vals[s + p] = sval[p] | entry_flags(p - b0, b1 - b0);
     }
   } else {
     for (uint32_t p = t; p < len; p += SORTB_THREADS) {
       const uint32_t key = keys2[s + p];
       if (key >= sent) continue;
-      const uint32_t pos = s + atomicAdd(&cur[key & mask], 1u);
-      keys[pos] = key;
-      vals[pos] = vals2[s + p];
+      const uint32_t d = key & mask;
+      const uint32_t b0 = off[d], b1 = d + 1 < D ? off[d + 1] : nz;
+      const uint32_t q = atomicAdd(&cur[d], 1u);
+      keys[s + q] = key;
+      vals[s + q] = vals2[s + p] | entry_flags(q - b0, b1 - b0);
     }
   }
   for (uint32_t p = nz + t; p < len; p += SORTB_THREADS) keys[s + p] = sent;

@@ -147,6 +147,7 @@ hipError_t msm_var(Arena& ar, hipStream_t s, const uint32_t* d_bases, const uint
     return hipMemcpyAsync(d_out, &inf, sizeof(inf), hipMemcpyHostToDevice, s);
   }
   if (n > MSM_MAX_POINTS) return hipErrorInvalidValue;
+  static_assert(2 * MSM_MAX_POINTS - 1 <= VAL_INDEX, "a GLV index must fit below the flags of a sorted value");
   const bool glv = n >= 64;  // phi(x, y) = (beta x, y) on G1, (beta^2 x, y) on G2
   // G1 with GLV: gather records of P and phi(P) (fetch_rec29) instead of phi(P) alone
   constexpr bool g1 = std::is_same<F, Fq>::value;
