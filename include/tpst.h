@@ -675,6 +675,109 @@ int tpst_r1cs_eval_stages(tpst_ctx* ctx, const tpst_r1cs_decomm* decomm, const u
                           const uint64_t* r_mem_check, const uint64_t* rand_ops, const uint64_t* rand_mem,
                           uint64_t* derefs, uint64_t* hash_ops, uint64_t* hash_mem, uint64_t* seg);
 
+/* ---- TestudoSnark / TestudoNizk (csrc/snark.hip) ----------------------------
+ * The composition of the calls above into the two end-to-end proofs of
+ * testudo_snark.rs:120-235 and testudo_nizk.rs:80-157, with the transcript
+ * calls between the parts that bind them.  Host code: every device stage is
+ * one of the entry points above, called without the context's lock held across
+ * them.  There is no prove_verifier: the Groth16 wrap stays replaced by the
+ * native checks of tpst_r1cs_verify_evals.
+ *
+ * Two sponges.  F = the caller's PoseidonTranscript<Fr> (`tr`), Q = a
+ * PoseidonTranscript<Fq> owned by the call.  The reference (commented out
+ * there) passes one PoseidonTranscript<ScalarField> to R1CSProof::prove, which
+ * since takes a PoseidonTranscript<BaseField> (r1csproof.rs:242); the bridge
+ * between the two is stated here.
+ *   SNARK prove:
+ *    1. tpst_r1cs_commitment_absorb(comm, F)        comm.write_to_transcript
+ *    2. c = F.challenge_scalar()
+ *    3. F.new_from_state(&c)                        tpst_transcript_fr_new_from_state
+ *    4. Q = fresh + new_from_state2(&c)             tpst_transcript_init, tpst_transcript_reset_fr
+ *                                                   (the Fr-into-Fq call of r1csproof.rs:262)
+ *    5. vars padded with zeros to num_vars          lib.rs:99-113
+ *    6. sat = tpst_r1cs_prove over Q -> rx, ry
+ *    7. inst_evals = tpst_r1cs_evaluate(rx, ry)
+ *    8. F absorbs append_scalar(sat.transcript_sat_state), append_scalar_vector(rx),
+ *       append_scalar_vector(ry), append_scalar(Ar), (Br), (Cr)   (testudo_snark.rs:156-162; the
+ *       reference binds by continuing on its one transcript)
+ *    9. tpst_r1cs_eval_prove(decomm, rx, ry, inst_evals, gens, F, rnd)
+ *   SNARK verify: 1-4 over the commitment; tpst_r1cs_verify_evals on Q with the
+ *   commitment's dimensions, the caller's inputs and the proof's inst_evals; the
+ *   absorbs of 8 from the proof's fields; tpst_r1cs_eval_verify at the proof's
+ *   (rx, ry).  It needs no instance and no decommitment.
+ *   NIZK prove: F.append_bytes(digest), 2-6, then the first three absorbs of 8,
+ *   so that the caller's transcript is bound to the proof.  NIZK verify mirrors
+ *   it and evaluates (A, B, C) itself (tpst_r1cs_verify).  The reference's NIZK
+ *   verifier omits the squeeze of c that its prover does (testudo_nizk.rs:90,
+ *   :144-147); this one mirrors the prover.
+ * Every call works on a copy of `tr` and stores it back only on TPST_OK; prover
+ * and verifier leave it in the same state.  Parity of the Fr transcript is
+ * unpinned against arkworks, as for the calls above.
+ *
+ * Errors.  TPST_E_ARG: a null argument, a value >= r, n_vars > num_vars,
+ * num_vars < 4, a handle of another context, an instance, commitment,
+ * decommitment or generators whose dimensions differ, a commitment point that
+ * is not canonical (provers), the assertions of tpst_r1cs_eval_prove.
+ * TPST_E_STATE: no SRS loaded for ceil(log2(num_vars) / 2) variables.
+ * TPST_E_VERIFY (verifiers): anything either verifier rejects -- a failed
+ * check, a malformed element of the proof, the inputs or the commitment, a
+ * number of inputs other than the commitment's. */
+
+/* append_u64 (poseidon_transcript.rs:65-67): one native absorb of the field
+ * element x (ark-crypto-primitives 0.4 `Absorb for u64`).  Host only. */
+int tpst_transcript_fr_append_u64(tpst_transcript_fr* t, uint64_t x);
+/* new_from_state (poseidon_transcript.rs:50-53): a fresh sponge that absorbs
+ * the scalar.  Host only; TPST_E_ARG for a value >= r. */
+int tpst_transcript_fr_new_from_state(tpst_transcript_fr* t, const uint64_t* fr);
+
+/* R1CSCommitment (r1csinstance.rs:55-61) as the caller holds it: the
+ * dimensions and the two row-commitment lists of tpst_r1cs_commit_decomm. */
+typedef struct {
+  size_t num_cons, num_vars, num_inputs, num_ops, num_mem_cells;
+  const uint64_t* comm_ops; /* ops_rows canonical affine G1 */
+  size_t ops_rows;
+  const uint64_t* comm_mem; /* mem_rows canonical affine G1 */
+  size_t mem_rows;
+} tpst_r1cs_commitment;
+/* R1CSCommitment::write_to_transcript (r1csinstance.rs:63-70, sparse_mlpoly.rs:
+ * 335-341, dense_mlpoly.rs:464-470): append_u64 of num_cons, num_vars,
+ * num_inputs, then of batch_size (3), num_ops, num_mem_cells, then append_point
+ * of every row of comm_comb_ops, then of comm_comb_mem.  Host only (one
+ * permutation or two per point).  TPST_E_ARG: a null pointer, row counts other
+ * than the ones num_ops / num_mem_cells imply, a point that is not canonical;
+ * `tr` is then untouched. */
+int tpst_r1cs_commitment_absorb(const tpst_r1cs_commitment* comm, tpst_transcript_fr* tr);
+
+/* The SNARK proof: (R1CSProof, inst_evals = (A, B, C)(rx, ry), R1CSEvalProof).
+ * rx and ry live in `sat`.  The variable parts of the evaluation proof stay
+ * caller-owned buffers, as for tpst_r1cs_eval_prove. */
+typedef struct {
+  tpst_r1cs_proof sat;
+  uint64_t inst_evals[3][4];
+  tpst_r1cs_eval_proof eval;
+} tpst_snark_proof;
+/* TestudoSnark::prove (testudo_snark.rs:120-196), steps 1-9 above.  vars =
+ * n_vars <= num_vars witness values (may be NULL when n_vars is 0); rnd_derefs /
+ * rnd_ops / rnd_mem and the three output buffers as tpst_r1cs_eval_prove takes
+ * them. */
+int tpst_snark_prove(tpst_ctx* ctx, tpst_r1cs* r1cs, const tpst_r1cs_commitment* comm,
+                     const tpst_r1cs_decomm* decomm, const tpst_r1cs_gens* gens, const uint64_t* vars, size_t n_vars,
+                     const uint64_t* inputs, const uint64_t* rnd_derefs, const uint64_t* rnd_ops,
+                     const uint64_t* rnd_mem, tpst_transcript_fr* tr, tpst_snark_proof* proof, uint64_t* comm_derefs,
+                     uint64_t* prod_ops, uint64_t* prod_mem);
+/* TestudoSnark::verify (testudo_snark.rs:198-235): TPST_OK only if both the
+ * satisfiability proof and the evaluation proof verify. */
+int tpst_snark_verify(tpst_ctx* ctx, const tpst_r1cs_commitment* comm, const tpst_r1cs_gens* gens,
+                      const uint64_t* inputs, size_t num_inputs, tpst_transcript_fr* tr,
+                      const tpst_snark_proof* proof, const uint64_t* comm_derefs, const uint64_t* prod_ops,
+                      const uint64_t* prod_mem);
+/* TestudoNizk::prove / verify (testudo_nizk.rs:80-157): digest = the instance's
+ * digest bytes (r1csinstance.rs:155-164), absorbed with append_bytes. */
+int tpst_nizk_prove(tpst_ctx* ctx, tpst_r1cs* r1cs, const uint8_t* digest, size_t digest_len, const uint64_t* vars,
+                    size_t n_vars, const uint64_t* inputs, tpst_transcript_fr* tr, tpst_r1cs_proof* proof);
+int tpst_nizk_verify(tpst_ctx* ctx, tpst_r1cs* r1cs, const uint8_t* digest, size_t digest_len,
+                     const uint64_t* inputs, tpst_transcript_fr* tr, const tpst_r1cs_proof* proof);
+
 /* ---- Groth16 over BLS12-377 (csrc/groth16.hip) ----
  * The prover behind R1CSProof::prove_verifier (r1csproof.rs:374-434,
  * Groth16::<E>::prove at :421): ark-groth16 create_proof with the
@@ -774,6 +877,27 @@ int tpst_ser_r1cs_eval_proof(const tpst_r1cs_eval_sizes* sizes, const tpst_r1cs_
 int tpst_de_r1cs_eval_proof(tpst_ctx* ctx, const uint8_t* in, size_t len, const tpst_r1cs_eval_sizes* sizes,
                             tpst_r1cs_eval_proof* proof, uint64_t* comm_derefs, uint64_t* prod_ops,
                             uint64_t* prod_mem);
+/* R1CSProof (r1csproof.rs:32-53) in declaration order: comm (nv = m_row),
+ * sc_proof_phase1, claims_phase2, sc_proof_phase2, eval_vars_at_ry,
+ * proof_eval_vars_at_ry, rx, ry, transcript_sat_state, initial_state, t,
+ * mipp_proof; the layout list is csrc/wire_snark.h.  r_abc and
+ * claims_phase2_z_abc are not fields of the reference's struct: not written,
+ * zero after a read, read by no verifier.  The writer is host only and takes
+ * the dimensions from the proof's own fields; the reader takes them from
+ * num_cons / num_vars and validates as the readers above (TPST_E_ARG also for
+ * an Fq12 coefficient >= p). */
+int tpst_ser_r1cs_proof(const tpst_r1cs_proof* proof, uint8_t* out, size_t cap, size_t* len);
+int tpst_de_r1cs_proof(tpst_ctx* ctx, const uint8_t* in, size_t len, size_t num_cons, size_t num_vars,
+                       tpst_r1cs_proof* proof);
+/* The SNARK proof = R1CSProof || R1CSEvalProof || Ar || Br || Cr.  This is
+ * this library's layout: the reference's TestudoSnark (testudo_snark.rs:22-29)
+ * would start with a Groth16 proof that is not produced here. */
+int tpst_ser_snark_proof(const tpst_r1cs_eval_sizes* sizes, const tpst_snark_proof* proof,
+                         const uint64_t* comm_derefs, const uint64_t* prod_ops, const uint64_t* prod_mem,
+                         uint8_t* out, size_t cap, size_t* len);
+int tpst_de_snark_proof(tpst_ctx* ctx, const uint8_t* in, size_t len, size_t num_cons, size_t num_vars,
+                        const tpst_r1cs_eval_sizes* sizes, tpst_snark_proof* proof, uint64_t* comm_derefs,
+                        uint64_t* prod_ops, uint64_t* prod_mem);
 /* inverse of tpst_ser_committer_key: flat = the tpst_srs_export layout, so
  * tpst_srs_load takes it.  With flat NULL and flat_cap 0 only *nv and
  * *flat_len are reported. */

@@ -141,6 +141,14 @@ PROTOTYPES = [
     ("tpst_r1cs_eval_verify", C.c_int, [_vp, _u64p, _u64p, _sz, _sz, _vp, _u64p, _u64p, _u64p, _vp, _vp, _u64p,
                                         _u64p, _u64p]),
     ("tpst_r1cs_eval_stages", C.c_int, [_vp, _vp, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p]),
+    ("tpst_transcript_fr_append_u64", C.c_int, [_vp, C.c_uint64]),
+    ("tpst_transcript_fr_new_from_state", C.c_int, [_vp, _u64p]),
+    ("tpst_r1cs_commitment_absorb", C.c_int, [_vp, _vp]),
+    ("tpst_snark_prove", C.c_int, [_vp, _vp, _vp, _vp, _vp, _u64p, _sz, _u64p, _u64p, _u64p, _u64p, _vp, _vp, _u64p,
+                                   _u64p, _u64p]),
+    ("tpst_snark_verify", C.c_int, [_vp, _vp, _vp, _u64p, _sz, _vp, _vp, _u64p, _u64p, _u64p]),
+    ("tpst_nizk_prove", C.c_int, [_vp, _vp, C.c_char_p, _sz, _u64p, _sz, _u64p, _vp, _vp]),
+    ("tpst_nizk_verify", C.c_int, [_vp, _vp, C.c_char_p, _sz, _u64p, _vp, _vp]),
     ("tpst_groth16_setup", C.c_int, [_vp, _vp, _u64p, C.POINTER(_vp)]),
     ("tpst_groth16_pk_free", None, [_vp]),
     ("tpst_groth16_domain", C.c_int, [_vp, C.POINTER(_sz)]),
@@ -168,6 +176,10 @@ PROTOTYPES = [
                                           _sz, C.POINTER(_sz)]),
     ("tpst_ser_r1cs_eval_proof", C.c_int, [_vp, _vp, _u64p, _u64p, _u64p, C.c_char_p, _sz, C.POINTER(_sz)]),
     ("tpst_de_r1cs_eval_proof", C.c_int, [_vp, C.c_char_p, _sz, _vp, _vp, _u64p, _u64p, _u64p]),
+    ("tpst_ser_r1cs_proof", C.c_int, [_vp, C.c_char_p, _sz, C.POINTER(_sz)]),
+    ("tpst_de_r1cs_proof", C.c_int, [_vp, C.c_char_p, _sz, _sz, _sz, _vp]),
+    ("tpst_ser_snark_proof", C.c_int, [_vp, _vp, _u64p, _u64p, _u64p, C.c_char_p, _sz, C.POINTER(_sz)]),
+    ("tpst_de_snark_proof", C.c_int, [_vp, C.c_char_p, _sz, _sz, _sz, _vp, _vp, _u64p, _u64p, _u64p]),
     ("tpst_de_committer_key", C.c_int, [_vp, C.c_char_p, _sz, C.POINTER(C.c_int), _u64p, _sz, C.POINTER(_sz)]),
     ("tpst_profile_enable", C.c_int, [_vp, C.c_int]),
     ("tpst_profile_reset", C.c_int, [_vp]),
@@ -267,6 +279,19 @@ class R1CSEvalSizes(C.Structure):
         ("prod_ops_len", _sz), ("prod_mem_len", _sz),
         ("rnd_len", _sz * 3),
     ]
+
+
+class R1CSCommitmentC(C.Structure):
+    """tpst_r1cs_commitment: the dimensions and row lists of an R1CSCommitment."""
+    _fields_ = [
+        ("num_cons", _sz), ("num_vars", _sz), ("num_inputs", _sz), ("num_ops", _sz), ("num_mem_cells", _sz),
+        ("comm_ops", _u64p), ("ops_rows", _sz), ("comm_mem", _u64p), ("mem_rows", _sz),
+    ]
+
+
+class SnarkProof(C.Structure):
+    """tpst_snark_proof: (R1CSProof, inst_evals, the fixed part of R1CSEvalProof)."""
+    _fields_ = [("sat", R1CSProof), ("inst_evals", (C.c_uint64 * 4) * 3), ("eval", R1CSEvalProof)]
 
 
 _lib = None

@@ -4,7 +4,8 @@
 // proof_size / commiter_key_size columns of benches/pst.rs:43-46,64-74.
 // Host-only code (no device work): the proof is a few KB.  The SPARK objects
 // at the end of this file (R1CSCommitment, R1CSEvalProof) and the CommitterKey
-// reader hold thousands of points: their readers validate on the device.
+// reader hold thousands of points: their readers validate on the device.  So do
+// the readers of R1CSProof and of the SNARK proof after them (wire_snark.h).
 //
 // Restated encoding rules (ark-serialize / ark-ff / ark-ec 0.4):
 //  * Fp: canonical value, little-endian, buffer_byte_size(MODULUS_BIT_SIZE +
@@ -28,6 +29,7 @@
 #include "ctx.h"
 #include "curve.h"
 #include "point_codec.h"
+#include "wire_snark.h"
 #include "wire_spark.h"
 
 using namespace tpst;
@@ -491,19 +493,28 @@ void write_items(Writer& w, const std::vector<wire::Item>& items, const uint64_t
         w.bytes(src + 4 * j, 32);
       } else if (it.kind == wire::G1) {
         put_g1_checked(w, src + 12 * j);
-      } else {
+      } else if (it.kind == wire::G2) {
         w.point<Fq2>(src + 24 * j);
+      } else {
+        w.gt(src + 72 * j);
       }
     }
   }
 }
 
-// the elements of a walked input into the caller's buffers: every Fr range-checked and copied, every
+// the elements of a walked input into the caller's buffers: every Fr and Fq12 range-checked and copied, every
 // point of `kind` decompressed and validated in one device batch.  TPST_E_ARG on any rejection.
 int read_items(tpst_ctx* ctx, const uint8_t* in, const std::vector<wire::Item>& items, const std::vector<size_t>& offs,
                uint64_t* const* bufs) {
   for (size_t i = 0; i < items.size(); i++) {
     const wire::Item& it = items[i];
+    if (it.kind == wire::GT) {  // 12 Fq each, no flags
+      uint64_t* dst = bufs[it.buf] + it.word;
+      memcpy(dst, in + offs[i], it.count * 576);
+      for (size_t j = 0; j < 12 * it.count; j++)
+        if (!lt_p(dst + 6 * j)) return fail(ctx, TPST_E_ARG, "wire format: Fq12 coefficient >= p");
+      continue;
+    }
     if (it.kind != wire::FR) continue;
     uint64_t* dst = bufs[it.buf] + it.word;
     memcpy(dst, in + offs[i], it.count * 32);
@@ -638,4 +649,90 @@ extern "C" int tpst_de_committer_key(tpst_ctx* ctx, const uint8_t* in, size_t le
     off += 2 * h * 24;
   }
   return TPST_OK;
+}
+
+// ================================================ R1CSProof, SNARK proof ==
+// The layouts are the item lists of wire_snark.h (restated there from
+// r1csproof.rs:32-53, sumcheck.rs:19-22, unipoly.rs:7-11, sqrt_pst.rs:201-204,
+// mipp.rs:21-28).  Elements are written and read by the routines above: the
+// same point, Fq12 and Fr codecs as Commitment, Proof and MippProof, the
+// points of a whole object validated in one device batch per group.
+namespace {
+
+wire::SatDims dims_of_proof(const tpst_r1cs_proof* p) {
+  return {p->rounds_x, p->rounds_y, p->open.m_col, p->open.m_row};
+}
+
+// the dimension fields of a proof just read
+void set_sat_dims(const wire::SatDims& d, tpst_r1cs_proof* p) {
+  p->rounds_x = d.rounds_x, p->rounds_y = d.rounds_y, p->num_vars_log = d.m_col + d.m_row;
+  p->open.m_col = d.m_col, p->open.m_row = d.m_row;
+}
+
+}  // namespace
+
+extern "C" int tpst_ser_r1cs_proof(const tpst_r1cs_proof* proof, uint8_t* out, size_t cap, size_t* len) {
+  std::vector<wire::Item> items;
+  if (!proof || proof->num_vars_log != proof->open.m_col + proof->open.m_row ||
+      !wire::r1cs_proof_items(dims_of_proof(proof), items))
+    return TPST_E_ARG;
+  const uint64_t* const bufs[1] = {reinterpret_cast<const uint64_t*>(proof)};
+  Writer w{out, cap};
+  write_items(w, items, bufs);
+  return finish(w, len);
+}
+
+extern "C" int tpst_de_r1cs_proof(tpst_ctx* ctx, const uint8_t* in, size_t len, size_t num_cons, size_t num_vars,
+                                  tpst_r1cs_proof* proof) {
+  if (!ctx || !in || !proof) return fail(ctx, TPST_E_ARG, "null argument");
+  wire::SatDims d;
+  std::vector<wire::Item> items;
+  std::vector<size_t> offs;
+  if (!wire::sat_dims(num_cons, num_vars, d) || !wire::r1cs_proof_items(d, items))
+    return fail(ctx, TPST_E_ARG, "wire format: dimensions no R1CSProof has");
+  if (!wire::walk_snark_items(in, len, items, offs)) return fail(ctx, TPST_E_ARG, "wire format: malformed R1CSProof");
+  memset(proof, 0, sizeof(*proof));
+  set_sat_dims(d, proof);
+  uint64_t* const bufs[1] = {reinterpret_cast<uint64_t*>(proof)};
+  return read_items(ctx, in, items, offs, bufs);
+}
+
+extern "C" int tpst_ser_snark_proof(const tpst_r1cs_eval_sizes* sizes, const tpst_snark_proof* proof,
+                                    const uint64_t* comm_derefs, const uint64_t* prod_ops, const uint64_t* prod_mem,
+                                    uint8_t* out, size_t cap, size_t* len) {
+  std::vector<wire::Item> items;
+  if (!sizes || !proof || !comm_derefs || !prod_ops || !prod_mem ||
+      proof->sat.num_vars_log != proof->sat.open.m_col + proof->sat.open.m_row ||
+      !wire::snark_items(dims_of_proof(&proof->sat), *sizes, items) || !rounds_ok(*sizes, &proof->eval))
+    return TPST_E_ARG;
+  const uint64_t* bufs[wire::S_NBUF];
+  bufs[wire::S_SAT] = reinterpret_cast<const uint64_t*>(&proof->sat);
+  bufs[wire::S_EVAL] = reinterpret_cast<const uint64_t*>(&proof->eval);
+  bufs[wire::S_DEREFS] = comm_derefs, bufs[wire::S_PROD_OPS] = prod_ops, bufs[wire::S_PROD_MEM] = prod_mem;
+  bufs[wire::S_EVALS] = &proof->inst_evals[0][0];
+  Writer w{out, cap};
+  write_items(w, items, bufs);
+  return finish(w, len);
+}
+
+extern "C" int tpst_de_snark_proof(tpst_ctx* ctx, const uint8_t* in, size_t len, size_t num_cons, size_t num_vars,
+                                   const tpst_r1cs_eval_sizes* sizes, tpst_snark_proof* proof, uint64_t* comm_derefs,
+                                   uint64_t* prod_ops, uint64_t* prod_mem) {
+  if (!ctx || !in || !sizes || !proof || !comm_derefs || !prod_ops || !prod_mem)
+    return fail(ctx, TPST_E_ARG, "null argument");
+  wire::SatDims d;
+  std::vector<wire::Item> items;
+  std::vector<size_t> offs;
+  if (!wire::sat_dims(num_cons, num_vars, d) || !wire::snark_items(d, *sizes, items))
+    return fail(ctx, TPST_E_ARG, "wire format: dimensions no proof has");
+  if (!wire::walk_snark_items(in, len, items, offs)) return fail(ctx, TPST_E_ARG, "wire format: malformed SNARK proof");
+  memset(proof, 0, sizeof(*proof));
+  set_sat_dims(d, &proof->sat);
+  set_rounds(*sizes, &proof->eval);
+  uint64_t* bufs[wire::S_NBUF];
+  bufs[wire::S_SAT] = reinterpret_cast<uint64_t*>(&proof->sat);
+  bufs[wire::S_EVAL] = reinterpret_cast<uint64_t*>(&proof->eval);
+  bufs[wire::S_DEREFS] = comm_derefs, bufs[wire::S_PROD_OPS] = prod_ops, bufs[wire::S_PROD_MEM] = prod_mem;
+  bufs[wire::S_EVALS] = &proof->inst_evals[0][0];
+  return read_items(ctx, in, items, offs, bufs);
 }
