@@ -311,6 +311,58 @@ int tpst_poly_open_sharded(tpst_ctx* ctx, tpst_poly* p, tpst_transcript* tr, int
 int tpst_pst_verify(tpst_ctx* ctx, tpst_transcript* tr, int n, const uint64_t* point, const uint64_t* v,
                     const uint64_t* T, const tpst_open_proof* proof);
 
+/* Batch verification: B openings of n-variable polynomials against the loaded
+ * SRS, decided by ONE combined check -- one multi-pairing with a single final
+ * exponentiation over B (3 + m_col + m_row) pairs, one GT-power launch over
+ * B (2 m_col + 1) bases and one G1 MSM over B (2 m_col + 2) points -- instead
+ * of B calls of tpst_pst_verify (three final exponentiations and a stream
+ * synchronisation each).  Every item is what one tpst_pst_verify call takes,
+ * with its own transcript (distinct per item).
+ *
+ * rho: four 128-bit multipliers per item, B x 4 x 2 u64 (little-endian limb
+ * pairs), in the order rho_T, rho_2, rho_1, rho_U: the weights of the item's T
+ * check, check_2, check and U check in the combination.  They are an argument,
+ * like every other random draw of this library, and THEY MUST BE DRAWN
+ * UNIFORMLY AT RANDOM AFTER ALL PROOFS OF THE BATCH ARE FIXED (a CSPRNG, never
+ * a value the prover can predict or influence, never reused across batches a
+ * prover sees): under that condition a batch that holds an invalid item passes
+ * with probability about 2^-128.  With predictable or repeated multipliers
+ * invalid items can be made to cancel each other.  A zero multiplier is
+ * TPST_E_ARG.
+ *
+ * Returns TPST_OK iff every item is valid, TPST_E_VERIFY otherwise; B == 0 is
+ * TPST_OK.  TPST_E_ARG: a null argument (items, rho, any field of an item),
+ * bad n, an item whose proof->m_col / m_row do not match n, a zero multiplier.
+ * TPST_E_STATE: no SRS loaded.
+ *
+ * Per item, as tpst_pst_verify: every element is validated before a sponge
+ * absorbs anything (scalars < r, Fq limbs < p, G1 / G2 points on their curve
+ * and in the subgroup, GT coefficients < p; T and comms_t in GT).  An item with
+ * a malformed element is invalid and left out of the combination; the others
+ * go on.
+ *
+ * ok (B bytes, or NULL): ok[j] = 1 iff item j is valid -- what tpst_pst_verify
+ * returns for it alone (up to the 2^-128 above).  When the combined check
+ * fails they are found by bisection over it.  With ok == NULL a failing batch
+ * returns TPST_E_VERIFY at once.
+ *
+ * Transcripts: a valid item's tr ends exactly as tpst_pst_verify leaves it; an
+ * invalid item's tr is untouched, also when the batch as a whole fails.  With
+ * ok == NULL and a failing combined check no verdicts exist and every tr is
+ * left untouched.
+ *
+ * The context lock is held once for the whole call.  Callers with one proof
+ * keep tpst_pst_verify. */
+typedef struct {
+  const uint64_t* point;        /* n Fr */
+  const uint64_t* v;            /* Fr */
+  const uint64_t* T;            /* GT */
+  const tpst_open_proof* proof;
+  tpst_transcript* tr;          /* this item's own transcript */
+} tpst_verify_item;
+int tpst_pst_verify_batch(tpst_ctx* ctx, int n, const tpst_verify_item* items, size_t B, const uint64_t* rho,
+                          uint8_t* ok);
+
 /* ---- MultilinearPC single calls (ark-poly-commit fork) --
  * Against the loaded SRS; a polynomial of nv <= ck.nv variables uses level
  * ck.nv - nv.  evals: 2^nv canonical Fr (to_evaluations order); point: nv Fr,
@@ -848,6 +900,21 @@ int tpst_de_g2_batch(tpst_ctx* ctx, const uint8_t* in, size_t n, uint64_t* out, 
 /* n canonical affine points -> TPST_OK, or TPST_E_VERIFY with *first_bad */
 int tpst_g1_check_batch(tpst_ctx* ctx, const uint64_t* pts, size_t n, size_t* first_bad);
 int tpst_g2_check_batch(tpst_ctx* ctx, const uint64_t* pts, size_t n, size_t* first_bad);
+
+/* ---- batched double-scalar multiplication (csrc/lincomb.hip) ----------------
+ * out[i] = s_i P_i + t_i Q_i for n pairs of canonical affine points (12 / 24
+ * u64 each, all-zero = infinity) and canonical Fr scalars; out: n canonical
+ * affine points.  Q and t may both be NULL: out[i] = s_i P_i.  One quad of
+ * lanes per output, joint double-and-add over the bit length of the longest
+ * scalar of the call (128-bit scalars cost half of full ones).  Every case is
+ * computed exactly: zero scalars, P = Q, P = -Q, inputs and results at
+ * infinity.  TPST_E_ARG: a null argument (or only one of Q, t), a scalar >= r,
+ * a non-canonical coordinate, a point off its curve.  Subgroup membership is
+ * not required (as for tpst_g1_msm).  n = 0 returns TPST_OK. */
+int tpst_g1_lincomb_batch(tpst_ctx* ctx, const uint64_t* P, const uint64_t* s, const uint64_t* Q, const uint64_t* t,
+                          size_t n, uint64_t* out);
+int tpst_g2_lincomb_batch(tpst_ctx* ctx, const uint64_t* P, const uint64_t* s, const uint64_t* Q, const uint64_t* t,
+                          size_t n, uint64_t* out);
 
 /* ---- arkworks wire format of the SPARK objects (csrc/serialize.hip) ---------
  * Compress::Yes, as above.  The writers are host only; the readers walk the

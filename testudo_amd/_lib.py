@@ -87,6 +87,7 @@ PROTOTYPES = [
     ("tpst_open_sharded_arena_bytes", _sz, [C.c_int, C.c_int]),
     ("tpst_poly_open_sharded", C.c_int, [_vp, _vp, _vp, C.c_int, _u64p, _u64p, _u64p, _vp, _vp]),
     ("tpst_pst_verify", C.c_int, [_vp, _vp, C.c_int, _u64p, _u64p, _u64p, _vp]),
+    ("tpst_pst_verify_batch", C.c_int, [_vp, C.c_int, _vp, _sz, _u64p, C.POINTER(C.c_uint8)]),
     ("tpst_mlpc_commit", C.c_int, [_vp, _u64p, C.c_int, _u64p]),
     ("tpst_mlpc_commit_g2", C.c_int, [_vp, _u64p, C.c_int, _u64p]),
     ("tpst_mlpc_open", C.c_int, [_vp, _u64p, C.c_int, _u64p, _u64p]),
@@ -170,6 +171,8 @@ PROTOTYPES = [
     ("tpst_de_g2_batch", C.c_int, [_vp, C.c_char_p, _sz, _u64p, C.POINTER(_sz)]),
     ("tpst_g1_check_batch", C.c_int, [_vp, _u64p, _sz, C.POINTER(_sz)]),
     ("tpst_g2_check_batch", C.c_int, [_vp, _u64p, _sz, C.POINTER(_sz)]),
+    ("tpst_g1_lincomb_batch", C.c_int, [_vp, _u64p, _u64p, _u64p, _u64p, _sz, _u64p]),
+    ("tpst_g2_lincomb_batch", C.c_int, [_vp, _u64p, _u64p, _u64p, _u64p, _sz, _u64p]),
     ("tpst_ser_r1cs_commitment", C.c_int, [_sz, _sz, _sz, _sz, _sz, _u64p, _sz, _u64p, _sz, C.c_char_p, _sz,
                                            C.POINTER(_sz)]),
     ("tpst_de_r1cs_commitment", C.c_int, [_vp, C.c_char_p, _sz, C.POINTER(_sz), _u64p, _sz, C.POINTER(_sz), _u64p,
@@ -206,6 +209,12 @@ class OpenProof(C.Structure):
         ("final_h", C.c_uint64 * 24),
         ("pst_proof_h", (C.c_uint64 * 12) * MAX_VARS),
     ]
+
+class VerifyItem(C.Structure):
+    """tpst_verify_item: one opening of tpst_pst_verify_batch."""
+    _fields_ = [("point", _u64p), ("v", _u64p), ("T", _u64p), ("proof", C.POINTER(OpenProof)),
+                ("tr", C.POINTER(Transcript))]
+
 
 # tpst_allgather_fn(user, send_off, recv_off, bytes, stream) -> 0 on success
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, _vp, _sz, _sz, _sz, _vp)

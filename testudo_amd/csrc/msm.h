@@ -54,6 +54,9 @@ enum MsmStage {
   ST_SPARSE_DEREF, ST_SPARSE_HASH_OPS, ST_SPARSE_HASH_MEM, ST_SPARSE_SEG_EVAL,
   // point_codec.hip: batched point decompression / validation (one launch per batch)
   ST_POINT_CODEC,
+  // lincomb.hip: k_lincomb2 launches (the batch verifier's and tpst_g*_lincomb_batch's);
+  // tpst_pst_verify_batch: its multi-pairing call (G2 preparation to the final exponentiation) and its GT powers
+  ST_LINCOMB, ST_VERIFY_BATCH_PAIRING, ST_VERIFY_BATCH_GT_POW,
   N_STAGES
 };
 

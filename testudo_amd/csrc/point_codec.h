@@ -26,6 +26,12 @@ int point_decompress_batch(tpst_ctx* ctx, const uint8_t* in, size_t n, uint64_t*
 template <class F>
 int point_check_batch(tpst_ctx* ctx, const uint64_t* pts, size_t n, size_t* first_bad);
 
+// the same launch for a caller that already holds the context lock (the batch
+// verifier): status[i] = 0 accepted, 1 rejected, for every point.  Stages in
+// ctx->io (reset here) and synchronises the stream.
+template <class F>
+int point_status_batch_locked(tpst_ctx* ctx, const uint64_t* pts, size_t n, uint8_t* status);
+
 // The verifiers' check of n row commitments (canonical affine G1, host memory):
 // the host loop on up to 16 threads below POINT_CHECK_DEVICE_MIN, the device
 // check from there.  *ok = every point is valid.  TPST_OK or TPST_E_HIP.

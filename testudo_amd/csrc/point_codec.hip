@@ -214,13 +214,9 @@ int point_decompress_batch(tpst_ctx* ctx, const uint8_t* in, size_t n, uint64_t*
 }
 
 template <class F>
-int point_check_batch(tpst_ctx* ctx, const uint64_t* pts, size_t n, size_t* first_bad) {
-  *first_bad = n;
+int point_status_batch_locked(tpst_ctx* ctx, const uint64_t* pts, size_t n, uint8_t* status) {
   if (n == 0) return TPST_OK;
   constexpr size_t W = Words<F>::n;
-  std::vector<uint8_t> st(n);
-  std::lock_guard<tpst::CtxMutex> lk(ctx->mu);
-  TPST_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   ctx->io.reset();
   TPST_HIP(ctx, ctx->io.reserve(Arena::need(n * 2 * W, 4) + Arena::need(n, 1)));
@@ -231,8 +227,19 @@ int point_check_batch(tpst_ctx* ctx, const uint64_t* pts, size_t n, size_t* firs
   k_point_check<F><<<grid_for(n, 64), 64, 0, s>>>(d_pts, n, d_st);
   ctx->prof.end(ST_POINT_CODEC, s);
   TPST_HIP(ctx, hipGetLastError());
-  TPST_HIP(ctx, hipMemcpyAsync(st.data(), d_st, n, hipMemcpyDeviceToHost, s));
+  TPST_HIP(ctx, hipMemcpyAsync(status, d_st, n, hipMemcpyDeviceToHost, s));
   TPST_HIP(ctx, hipStreamSynchronize(s));
+  return TPST_OK;
+}
+
+template <class F>
+int point_check_batch(tpst_ctx* ctx, const uint64_t* pts, size_t n, size_t* first_bad) {
+  *first_bad = n;
+  if (n == 0) return TPST_OK;
+  std::vector<uint8_t> st(n);
+  std::lock_guard<tpst::CtxMutex> lk(ctx->mu);
+  TPST_HIP(ctx, hipSetDevice(ctx->device));
+  if (int rc = point_status_batch_locked<F>(ctx, pts, n, st.data())) return rc;
   *first_bad = first_set(st);
   return TPST_OK;
 }
@@ -273,6 +280,8 @@ template int point_decompress_batch<Fq>(tpst_ctx*, const uint8_t*, size_t, uint6
 template int point_decompress_batch<Fq2>(tpst_ctx*, const uint8_t*, size_t, uint64_t*, size_t*);
 template int point_check_batch<Fq>(tpst_ctx*, const uint64_t*, size_t, size_t*);
 template int point_check_batch<Fq2>(tpst_ctx*, const uint64_t*, size_t, size_t*);
+template int point_status_batch_locked<Fq>(tpst_ctx*, const uint64_t*, size_t, uint8_t*);
+template int point_status_batch_locked<Fq2>(tpst_ctx*, const uint64_t*, size_t, uint8_t*);
 
 }  // namespace tpst
 

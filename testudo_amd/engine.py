@@ -106,6 +106,29 @@ class Context:
                    "tpst_g2_mul_generator")
         return out
 
+    def _lincomb(self, fn, w, P, s, Q, t, what):
+        P = np.ascontiguousarray(P, dtype=np.uint64).reshape(-1, w)
+        s = np.ascontiguousarray(s, dtype=np.uint64).reshape(-1, 4)
+        if (Q is None) != (t is None) or len(s) != len(P):
+            raise TpstError(what + ": Q and t go together; one scalar per point")
+        if Q is not None:
+            Q = np.ascontiguousarray(Q, dtype=np.uint64).reshape(-1, w)
+            t = np.ascontiguousarray(t, dtype=np.uint64).reshape(-1, 4)
+            if len(Q) != len(P) or len(t) != len(P):
+                raise TpstError(what + ": length mismatch")
+        out = np.zeros((len(P), w), dtype=np.uint64)
+        self.check(fn(self.h, ptr(P), ptr(s), None if Q is None else ptr(Q), None if t is None else ptr(t), len(P),
+                      ptr(out)), what)
+        return out
+
+    def g1_lincomb_batch(self, P, s, Q=None, t=None) -> np.ndarray:
+        """out[i] = s_i P_i + t_i Q_i on G1 (tpst_g1_lincomb_batch); Q = t = None: s_i P_i.  (n, 12)."""
+        return self._lincomb(self.lib.tpst_g1_lincomb_batch, 12, P, s, Q, t, "tpst_g1_lincomb_batch")
+
+    def g2_lincomb_batch(self, P, s, Q=None, t=None) -> np.ndarray:
+        """out[i] = s_i P_i + t_i Q_i on G2 (tpst_g2_lincomb_batch).  (n, 24)."""
+        return self._lincomb(self.lib.tpst_g2_lincomb_batch, 24, P, s, Q, t, "tpst_g2_lincomb_batch")
+
     # ------------------------------------------------------- profiling ---
     STAGES = ("decompose", "sort", "bounds", "bucket_acc", "reduce", "combine", "batch_sort",
               # sqrt-PST stages under the reference's Timer labels (sqrt_pst.rs:33-262), device spans
@@ -118,7 +141,9 @@ class Context:
               # tpst_r1cs_eval_prove: k_deref; k_hash_ops; k_hash_mem; k_seg_eval (both groups, with their sums)
               "sparse_deref", "sparse_hash_ops", "sparse_hash_mem", "sparse_seg_eval",
               # point_codec.hip: batched point decompression / validation
-              "point_codec")
+              "point_codec",
+              # k_lincomb2 launches; tpst_pst_verify_batch's multi-pairing call and its GT powers
+              "lincomb", "verify_batch_pairing", "verify_batch_gt_pow")
 
     def profile(self, on: bool):
         self.check(self.lib.tpst_profile_enable(self.h, 1 if on else 0), "tpst_profile_enable")

@@ -447,6 +447,61 @@ def verify(ctx: Context, transcript: PoseidonTranscript, U, point, v, pst_proof,
     return True
 
 
+def pack_items(items):
+    """(transcript, U, point, v, pst_proof, mipp, T) tuples -> (n, the
+    tpst_verify_item array, the arrays it points into -- keep them alive for
+    the call)."""
+    B = len(items)
+    n = len(_u64(items[0][2]).reshape(-1, 4))
+    arr = (_lib.VerifyItem * B)()
+    keep = []
+    for j, (tr, U, point, v, pst_proof, mipp, T) in enumerate(items):
+        point = _u64(point).reshape(-1, 4)
+        if len(point) != n:
+            raise TpstError("items of one batch share the number of variables")
+        v, T = _u64(v, (4,)), _u64(T, (72,))
+        pr = pack_proof(n, U, pst_proof, mipp)
+        keep.append((point, v, T, pr, tr))
+        arr[j].point, arr[j].v, arr[j].T = ptr(point), ptr(v), ptr(T)
+        arr[j].proof = C.pointer(pr)
+        arr[j].tr = C.pointer(tr.t)
+    return n, arr, keep
+
+
+def verify_batch(ctx: Context, items, rho=None):
+    """tpst_pst_verify_batch: one combined check of many openings against the
+    SRS loaded in ``ctx``.  ``items``: a sequence of (transcript, U, point, v,
+    pst_proof, mipp, T) -- the arguments of ``verify``, one PoseidonTranscript
+    per item.  ``rho``: (B, 4, 2) uint64, the 128-bit multipliers (rho_T,
+    rho_2, rho_1, rho_U) of every item; None draws them here with ``secrets``.
+    A caller that passes its own must draw them uniformly at random after all
+    proofs of the batch are fixed (include/tpst.h).  Returns (all valid, ok)
+    with ok a (B,) uint8 array of per-item verdicts; valid items' transcripts
+    are advanced as ``verify`` advances them, invalid ones are untouched."""
+    items = list(items)
+    B = len(items)
+    if B == 0:
+        return True, np.zeros(0, dtype=np.uint8)
+    if rho is None:
+        import secrets
+        rho = np.zeros((B, 4, 2), dtype=np.uint64)
+        for j in range(B):
+            for k in range(4):
+                x = 0
+                while x == 0:
+                    x = secrets.randbits(128)
+                rho[j, k] = (x & (2**64 - 1), x >> 64)
+    rho = _u64(rho, (B, 4, 2))
+    n, arr, _keep = pack_items(items)
+    ok = np.zeros(B, dtype=np.uint8)
+    rc = ctx.lib.tpst_pst_verify_batch(ctx.h, n, C.cast(arr, C.c_void_p), B, ptr(rho),
+                                       ok.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if rc == -5:
+        return False, ok
+    ctx.check(rc, "verify_batch")
+    return True, ok
+
+
 def g1_msm_partial_into(ctx: Context, d_bases: int, d_scalars: int, i0: int, i1: int, out) -> None:
     """Points [i0, i1) of a device-resident MSM (Montgomery bases, canonical Fr
     scalars) summed into the int64 tensor ``out`` (24 words, raw XYZZ; a host
