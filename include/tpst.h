@@ -1036,6 +1036,35 @@ int tpst_selftest_curve(tpst_ctx* ctx, int op, size_t n, const uint64_t* p, cons
  * b is read by F12_MUL and GT_POW only and may be null otherwise.  A bad op, a
  * null pointer, n == 0 or n > 2^16 is TPST_E_ARG. */
 int tpst_selftest_tower(tpst_ctx* ctx, int op, size_t n, const uint64_t* a, const uint64_t* b, uint64_t* out);
+/* Self-test of the fixed-base table engine (csrc/fbt.h): the opening's own
+ * fbt_build and fbt_msm on caller-chosen bases, scalars and groups, with
+ * everything an FbGroups can say.  No kernel of its own.
+ *   group 1 / 2: G1 / G2.  glv 0 / 1: the plain table (64 windows per base) or
+ *     the GLV table (32 windows, G1 only: glv = 1 with group = 2 is
+ *     TPST_E_ARG).
+ *   bases: n canonical affine points in tpst_g1_msm's layout (12 / 24 u64 each,
+ *     infinity = all zero), 1 <= n <= 2^14.
+ *   mode 0, the grouped MSM: scalars = n_scalars canonical Fr (4 u64 each,
+ *     1 <= n_scalars <= 2^20); out[q groups + g] = sum over the members m <
+ *     `members` of group g of scalars[k + q set_stride] * bases[k], as
+ *     canonical affine points (sets * groups of them), where
+ *       seg == NULL (strided): k = (m / D) L + g D + m % D;
+ *       seg != NULL: groups + 1 u32, k = seg[g] + m for m < seg[g+1] - seg[g]
+ *         (L and D are not read; an empty segment gives infinity).
+ *     Checked on the host before anything is launched, each violation
+ *     TPST_E_ARG: groups, sets >= 1; sets * groups * max(members, 1) <= 2^16;
+ *     strided: 1 <= L, D <= 2^14; every k is below n and every k + q set_stride
+ *     below n_scalars (set_stride <= 2^20); seg is non-decreasing, ends at or
+ *     below n, and no segment is longer than `members`.  members = 0 is
+ *     allowed and gives infinity.
+ *   mode 1, the table: scalars, the group arguments and seg are not read;
+ *     out = the n * nw * 8 table entries as canonical affine points, nw = 64
+ *     (plain) or 32 (GLV): entry ((k nw + w) 8 + m) = (m + 1) 16^w bases[k].
+ * A null ctx, bases or out, a group, glv or mode outside the values above, or
+ * n outside its range is TPST_E_ARG. */
+int tpst_selftest_fbt(tpst_ctx* ctx, int group, int glv, int mode, const uint64_t* bases, size_t n,
+                      const uint64_t* scalars, size_t n_scalars, size_t groups, size_t members, size_t L, size_t D,
+                      const uint32_t* seg, size_t sets, size_t set_stride, uint64_t* out);
 
 /* Per-stage HIP-event timing of the MSM pipeline on the context's stream.
  * stage: 0 decompose, 1 sort, 2 bucket bounds, 3 bucket accumulation (the

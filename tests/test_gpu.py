@@ -90,12 +90,54 @@ def test_msm_truncates_like_msm_unchecked(ctx):
     assert np.array_equal(ctx.g1_msm(bases, s), orc.g1_msm(bases, s[:50]))
 
 
-def test_g2_msm_vs_oracle(ctx):
-    for n in (1, 17, 300):
-        s, _ = orc.fr_stream(3000 + n, n)
-        k, _ = orc.fr_stream(4000 + n, n)
-        bases = orc.g2_mul_gen(k)
-        assert np.array_equal(ctx.g2_msm(bases, s), orc.g2_msm(bases, s))
+@pytest.mark.parametrize("n", [0, 1, 2, 17, 63, 64, 65, 128, 129, 300, 1024, 1025])
+def test_g2_msm_vs_oracle(ctx, n):
+    """no GLV below 64 points, GLV from 64 (2 n sort entries), and the window
+    sizes of msm_window_bits(2 n): c = 4 up to n = 64, 7 from 65, 10 from 1025"""
+    s, _ = orc.fr_stream(3000 + n, max(n, 1))
+    k, _ = orc.fr_stream(4000 + n, max(n, 1))
+    bases = orc.g2_mul_gen(k)[:n]
+    s = s[:n]
+    assert np.array_equal(ctx.g2_msm(bases, s), orc.g2_msm(bases, s))
+
+
+def test_g2_msm_edge_scalars_and_collisions(ctx):
+    """the G2 twin of test_g1_msm_edge_scalars_and_collisions"""
+    n = 300
+    k, _ = orc.fr_stream(33, n)
+    bases = orc.g2_mul_gen(k)
+    bases[10] = 0                      # infinity base
+    bases[20:40] = bases[50]           # repeated bases -> same-bucket collisions
+    vals = [0, 1, 2, O.R - 1, O.R - 2, (1 << 252), (1 << 16), (1 << 15) - 1, (1 << 15), (1 << 15) + 1]
+    s = fr_array(vals * (n // len(vals)))
+    assert np.array_equal(ctx.g2_msm(bases, s), orc.g2_msm(bases, s))
+    # all-equal scalars: every point in one bucket per window
+    s2 = fr_array([12345678901234567890123] * n)
+    assert np.array_equal(ctx.g2_msm(bases, s2), orc.g2_msm(bases, s2))
+    # P + (-P) cancellation inside one bucket
+    neg = g2_array([None if p is None else (p[0], tuple((O.P - c) % O.P for c in p[1]))
+                    for p in g2_from_array(bases[:2])])
+    b3 = np.concatenate([bases[:2], neg])
+    s3 = fr_array([5, 9, 5, 9])
+    assert not orc.g2_msm(b3, s3).any()
+    assert not ctx.g2_msm(b3, s3).any()
+
+
+def test_g2_msm_linearity_16bit_windows(ctx):
+    """n = 2^18 + 5, the smallest G2 size with 16-bit windows (2 n > 2^19 sort
+    entries, 32768 buckets per window): MSM(k_i G2) == (sum s_i k_i) G2, on
+    uniform scalars and on 0 / 1 / 2 scalars (two long buckets in window 0)"""
+    n = (1 << 18) + 5
+    k, _ = orc.fr_stream(91, n)
+    bases = ctx.g2_mul_generator(k)
+    ki = [limbs_to_int(r) for r in k]
+    s, _ = orc.fr_stream(92, n)
+    rng = np.random.default_rng(93)
+    s2 = np.zeros((n, 4), dtype=np.uint64)
+    s2[:, 0] = rng.integers(0, 3, n, dtype=np.uint64)
+    for name, sc in (("uniform", s), ("0/1/2", s2)):
+        tot = sum(limbs_to_int(a) * b for a, b in zip(sc, ki)) % O.R
+        assert np.array_equal(ctx.g2_msm(bases, sc), orc.g2_mul_gen(fr_array([tot]))[0]), name
 
 
 @pytest.mark.parametrize("lg", [16, 20, 21])

@@ -56,6 +56,8 @@ PROTOTYPES = [
     ("tpst_selftest_field", C.c_int, [_vp, C.c_int, _sz, _u64p, _u64p, _u64p]),
     ("tpst_selftest_curve", C.c_int, [_vp, C.c_int, _sz, _u64p, _u64p, _u64p]),
     ("tpst_selftest_tower", C.c_int, [_vp, C.c_int, _sz, _u64p, _u64p, _u64p]),
+    ("tpst_selftest_fbt", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _u64p, _sz, _u64p, _sz, _sz, _sz, _sz, _sz,
+                                    C.POINTER(C.c_uint32), _sz, _sz, _u64p]),
     ("tpst_transcript_init", None, [_vp]),
     ("tpst_transcript_append_g1", C.c_int, [_vp, _u64p]),
     ("tpst_transcript_append_gt", C.c_int, [_vp, _u64p]),

@@ -1,7 +1,8 @@
 // Self-tests of the device arithmetic below the kernels (tpst_selftest_field /
 // tpst_selftest_curve): element-wise runs of the building blocks
 // (selftest_ops.h) on caller-chosen operands; and of the pairing's two Fq12
-// engines (tpst_selftest_tower, at the end).  64-thread blocks, every lane
+// engines (tpst_selftest_tower); and of the fixed-base table engine
+// (tpst_selftest_fbt, at the end).  64-thread blocks, every lane
 // active: the threads past the last element recompute it and store nothing,
 // which keeps the quads of coop.h and the pairs of pair_fq2.h whole.
 //
@@ -14,6 +15,7 @@
 #include "device_util.h"
 #include "acc_field.h"
 #include "coop.h"
+#include "fbt.h"
 #include "pair_fq2.h"
 #include "glv.h"
 #include "pairing_kernels.h"
@@ -381,4 +383,107 @@ extern "C" int tpst_selftest_tower(tpst_ctx* ctx, int op, size_t n, const uint64
   TPST_HIP(ctx, hipMemcpyAsync(out, d_o, (n * wo + nok) * 4, hipMemcpyDeviceToHost, s));
   TPST_HIP(ctx, hipStreamSynchronize(s));
   return TPST_OK;
+}
+
+// ---- the fixed-base table engine (tpst_selftest_fbt) ------------------------
+// fbt_build / fbt_msm (fbt.h) themselves on a caller-chosen FbGroups: no kernel
+// of its own.  Every index a kernel will form is checked here first.
+constexpr size_t ST_FBT_MAX_N = (size_t)1 << 14;        // bases (a table is 48 KiB per G1 base, 96 KiB per G2 base)
+constexpr size_t ST_FBT_MAX_SCALARS = (size_t)1 << 20;  // scalars, and the bound on set_stride
+constexpr size_t ST_FBT_MAX_TERMS = (size_t)1 << 16;    // sets * groups * max(members, 1)
+
+// true when every (set, group, member) reads a base below n and a scalar below n_scalars
+static bool fbt_groups_in_bounds(size_t n, size_t n_scalars, const FbGroups& g, const uint32_t* seg) {
+  if (!g.groups || !g.sets || g.groups > ST_FBT_MAX_TERMS || g.sets > ST_FBT_MAX_TERMS ||
+      g.members > ST_FBT_MAX_TERMS)
+    return false;
+  if (g.sets * g.groups > ST_FBT_MAX_TERMS || g.sets * g.groups * (g.members ? g.members : 1) > ST_FBT_MAX_TERMS)
+    return false;
+  if (g.set_stride > ST_FBT_MAX_SCALARS) return false;
+  size_t kmax = 0;  // largest base index any member reads
+  bool any = false;
+  if (seg) {
+    for (size_t i = 0; i < g.groups; i++) {
+      if (seg[i] > seg[i + 1] || (size_t)seg[i + 1] - seg[i] > g.members) return false;
+    }
+    if (seg[g.groups] > n) return false;
+    any = seg[g.groups] > seg[0];
+    if (any) kmax = (size_t)seg[g.groups] - 1;
+  } else {
+    if (!g.L || !g.D || g.L > ST_FBT_MAX_N || g.D > ST_FBT_MAX_N) return false;
+    for (size_t i = 0; i < g.groups; i++)
+      for (size_t m = 0; m < g.members; m++) {
+        const size_t k = (m / g.D) * g.L + i * g.D + m % g.D;
+        if (k >= n) return false;
+        if (k > kmax) kmax = k;
+        any = true;
+      }
+  }
+  return !any || kmax + (g.sets - 1) * g.set_stride < n_scalars;
+}
+
+template <class F>
+static int selftest_fbt(tpst_ctx* ctx, bool glv, int mode, const uint64_t* bases, size_t n, const uint64_t* scalars,
+                        size_t n_scalars, const FbGroups& g0, const uint32_t* seg, uint64_t* out) {
+  constexpr size_t PW = 2 * Words<F>::n;
+  const size_t nw = glv ? FBT_WG : FBT_W;
+  const size_t entries = n * nw * FBT_M, G = mode ? 0 : g0.groups * g0.sets;
+  const size_t nout = mode ? entries : G;
+  std::lock_guard<tpst::CtxMutex> lk(ctx->mu);
+  TPST_HIP(ctx, hipSetDevice(ctx->device));
+  ctx->io.reset();
+  TPST_HIP(ctx, ctx->io.reserve(Arena::need(n * PW, 4) * 2 + Arena::need(n_scalars * 8, 4) +
+                                Arena::need(g0.groups + 1, 4) + Arena::need(G, sizeof(Xyzz<F>)) +
+                                Arena::need(nout * PW, 4) + Arena::need(entries * PW, 4) + 4096));
+  uint32_t* d_b = ctx->io.take<uint32_t>(n * PW);
+  uint32_t* d_bm = ctx->io.take<uint32_t>(n * PW);
+  uint32_t* d_s = ctx->io.take<uint32_t>(n_scalars * 8);
+  uint32_t* d_seg = ctx->io.take<uint32_t>(g0.groups + 1);
+  Xyzz<F>* d_r = ctx->io.take<Xyzz<F>>(G);
+  uint32_t* d_o = ctx->io.take<uint32_t>(nout * PW);
+  uint32_t* d_t = ctx->io.take<uint32_t>(entries * PW);
+  hipStream_t s = ctx->stream;
+  TPST_HIP(ctx, hipMemcpyAsync(d_b, bases, n * PW * 4, hipMemcpyHostToDevice, s));
+  TPST_HIP(ctx, points_to_mont<F>(s, d_b, d_bm, n));
+  TPST_HIP(ctx, fbt_build<F>(ctx->arena, s, d_bm, n, d_t, glv));
+  if (mode) {
+    TPST_HIP(ctx, affine_from_mont<F>(s, d_t, d_o, entries));
+  } else {
+    FbGroups g = g0;
+    TPST_HIP(ctx, hipMemcpyAsync(d_s, scalars, n_scalars * 32, hipMemcpyHostToDevice, s));
+    if (seg) {
+      TPST_HIP(ctx, hipMemcpyAsync(d_seg, seg, (g.groups + 1) * 4, hipMemcpyHostToDevice, s));
+      g.d_seg = d_seg;
+    }
+    TPST_HIP(ctx, fbt_msm<F>(ctx->arena, s, d_t, d_s, g, d_r));
+    TPST_HIP(ctx, xyzz_to_affine_canonical<F>(s, d_r, d_o, G));
+  }
+  TPST_HIP(ctx, hipMemcpyAsync(out, d_o, nout * PW * 4, hipMemcpyDeviceToHost, s));
+  TPST_HIP(ctx, hipStreamSynchronize(s));
+  return TPST_OK;
+}
+
+extern "C" int tpst_selftest_fbt(tpst_ctx* ctx, int group, int glv, int mode, const uint64_t* bases, size_t n,
+                                 const uint64_t* scalars, size_t n_scalars, size_t groups, size_t members, size_t L,
+                                 size_t D, const uint32_t* seg, size_t sets, size_t set_stride, uint64_t* out) {
+  if (!ctx || !bases || !out || !n || n > ST_FBT_MAX_N || (group != 1 && group != 2) || (glv != 0 && glv != 1) ||
+      (mode != 0 && mode != 1) || (glv && group == 2))
+    return fail(ctx, TPST_E_ARG, "bad argument");
+  FbGroups g;
+  g.glv = glv != 0;
+  if (mode == 0) {
+    g.groups = groups;
+    g.members = members;
+    g.L = L;
+    g.D = D;
+    g.sets = sets;
+    g.set_stride = set_stride;
+    if (!scalars || !n_scalars || n_scalars > ST_FBT_MAX_SCALARS || !fbt_groups_in_bounds(n, n_scalars, g, seg))
+      return fail(ctx, TPST_E_ARG, "bad group shape");
+  } else {
+    n_scalars = 0;
+    seg = nullptr;
+  }
+  return group == 2 ? selftest_fbt<Fq2>(ctx, false, mode, bases, n, scalars, n_scalars, g, seg, out)
+                    : selftest_fbt<Fq>(ctx, g.glv, mode, bases, n, scalars, n_scalars, g, seg, out);
 }

@@ -265,6 +265,34 @@ class Context:
         res = out[:n * wo].reshape(n, wo)
         return (res, out[n * wo:n * wo + n]) if nok else res
 
+    def selftest_fbt(self, bases: np.ndarray, scalars: np.ndarray = None, *, g2: bool = False, glv: bool = False,
+                     groups: int = 1, members: int = 0, L: int = 1, D: int = 1, seg=None, sets: int = 1,
+                     set_stride: int = 0, table: bool = False) -> np.ndarray:
+        """the fixed-base table engine (csrc/fbt.h) on a caller-chosen FbGroups
+        (include/tpst.h tpst_selftest_fbt): (sets * groups, 12|24) canonical
+        affine sums, or with table=True the (n * nw * 8, 12|24) table entries.
+        The group shape is not checked here: the library validates it and a
+        violation raises TpstError."""
+        w = 24 if g2 else 12
+        bases = np.ascontiguousarray(bases, dtype=np.uint64).reshape(-1, w)
+        n = len(bases)
+        if table:
+            out = np.zeros((n * (32 if glv else 64) * 8, w), dtype=np.uint64)
+            s_ptr, ns = None, 0
+        else:
+            scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+            s_ptr, ns = ptr(scalars), len(scalars)
+            out = np.zeros((max(sets * groups, 0), w), dtype=np.uint64)
+        seg_ptr = None
+        if seg is not None:
+            seg = np.ascontiguousarray(seg, dtype=np.uint32)
+            assert seg.shape == (groups + 1,)  # what the library will read
+            seg_ptr = seg.ctypes.data_as(C.POINTER(C.c_uint32))
+        self.check(self.lib.tpst_selftest_fbt(self.h, 2 if g2 else 1, int(glv), int(table), ptr(bases), n, s_ptr, ns,
+                                              groups, members, L, D, seg_ptr, sets, set_stride, ptr(out)),
+                   "tpst_selftest_fbt")
+        return out
+
 
 def _u32ptr(a: np.ndarray):
     assert a.dtype == np.uint32 and a.flags["C_CONTIGUOUS"] and a.size % 2 == 0
