@@ -363,6 +363,72 @@ typedef struct {
 int tpst_pst_verify_batch(tpst_ctx* ctx, int n, const tpst_verify_item* items, size_t B, const uint64_t* rho,
                           uint8_t* ok);
 
+/* Combined opening: B polynomials of the same n (1 <= B <= 256), committed one
+ * by one, opened at ONE common point with ONE proof.  No counterpart in the
+ * reference.  The commitment is linear in the polynomial (the row list and
+ * T), so for weights w (B canonical Fr)
+ *   Z* = sum_j w_j Z_j,   comm_list*[i] = sum_j w_j comm_list_j[i],
+ *   T* = prod_j T_j^(w_j), v* = sum_j w_j v_j
+ * is a committed polynomial and its value at the point; one ordinary opening
+ * of Z* against (comm_list*, T*) proves all B values.  The verifier forms T*
+ * and v* from the B commitments T_j and the claimed v_j and runs the ordinary
+ * verifier once.
+ *
+ * SOUNDNESS: the weights are an argument, like every other draw of this
+ * library, and THEY MUST BE FIXED ONLY AFTER EVERY T_j, THE POINT AND EVERY
+ * CLAIMED v_j ARE FIXED: either derived from a transcript that has absorbed
+ * all of them (tpst_pst_combine_challenge, called at the same place by prover
+ * and verifier) or drawn uniformly at random by the verifier afterwards.  With
+ * weights the prover can predict, wrong values can be made to cancel in v*.
+ *
+ * tpst_poly_lincomb: a new whole-polynomial handle holding Z* (free it with
+ *   tpst_poly_free).  Arithmetic only: zero weights are allowed.  TPST_E_ARG:
+ *   null argument, B out of range, differing n, a weight >= r, a handle of
+ *   another context; TPST_E_STATE: a handle that is not a whole polynomial
+ *   (tpst_poly_from_evaluations_cols, tpst_poly_from_q_dev).
+ * tpst_g1_lincomb_rows: out[i] = sum_j w_j lists[j][i] for i < C (C >= 1,
+ *   B C <= 2^26); lists[j] = C canonical affine G1, all-zero = infinity;
+ *   validation as tpst_g1_lincomb_batch (canonical, on the curve, no subgroup
+ *   test).  The doublings of the chain are shared by all B terms and it is as
+ *   long as the longest weight: 128-bit weights cost half.
+ * tpst_commit_lincomb: the combined row list (comms[j] = 2^m_col G1 ->
+ *   comms_out), the combined T (Ts[j] = GT -> T_out), or both; comms or Ts may
+ *   be NULL (with its output), not both -- the verifier has only the T_j.
+ *   TPST_E_ARG as above, and for a T_j with a coefficient >= p or outside GT.
+ * tpst_pst_combine_challenge: host only.  The Fiat-Shamir weights: on the
+ *   caller's transcript, append_gt of T_0..T_{B-1}, tpst_transcript_append_fr
+ *   of the n point coordinates and of v_0..v_{B-1}, one challenge rho;
+ *   w_j = rho^j (w_0 = 1).  TPST_E_ARG: null argument, B out of range, a
+ *   coordinate or value >= r.
+ * tpst_poly_open_combined: tpst_poly_lincomb, tpst_commit_lincomb,
+ *   tpst_poly_eval and tpst_poly_open of the combination, under those calls'
+ *   rules; writes comm_list* (2^m_col G1), T*, v* and the proof.  A zero
+ *   weight is TPST_E_ARG (that polynomial would not be bound).  tr ends
+ *   exactly as tpst_poly_open of Z* leaves it.
+ * tpst_pst_verify_combined: T* and v* from (Ts, vs, w), then tpst_pst_verify.
+ *   TPST_OK or TPST_E_VERIFY -- the latter also for a v_j or w_j >= r, a zero
+ *   weight, a T_j with a coefficient >= p or outside GT, all checked before the
+ *   sponge absorbs anything.  tr is changed only on TPST_OK, and then as
+ *   tpst_pst_verify on (T*, v*) leaves it.  TPST_E_ARG: null argument, B out
+ *   of range, sizes that do not match n; TPST_E_STATE: no SRS loaded. */
+int tpst_poly_lincomb(tpst_ctx* ctx, tpst_poly* const* polys, size_t B, const uint64_t* w, tpst_poly** out);
+/* The 2^n evaluations of a whole polynomial (canonical Fr, the order of
+ * tpst_poly_from_evaluations) copied to the host, e.g. Z* of tpst_poly_lincomb.
+ * TPST_E_STATE: not a whole polynomial. */
+int tpst_poly_evaluations(tpst_ctx* ctx, const tpst_poly* p, uint64_t* Z);
+int tpst_g1_lincomb_rows(tpst_ctx* ctx, const uint64_t* const* lists, size_t B, size_t C, const uint64_t* w,
+                         uint64_t* out);
+int tpst_commit_lincomb(tpst_ctx* ctx, int n, const uint64_t* const* comms, const uint64_t* const* Ts, size_t B,
+                        const uint64_t* w, uint64_t* comms_out, uint64_t* T_out);
+int tpst_pst_combine_challenge(tpst_transcript* tr, int n, const uint64_t* point, const uint64_t* const* Ts,
+                               const uint64_t* vs, size_t B, uint64_t* w_out);
+int tpst_poly_open_combined(tpst_ctx* ctx, tpst_poly* const* polys, const uint64_t* const* comms,
+                            const uint64_t* const* Ts, size_t B, const uint64_t* w, tpst_transcript* tr,
+                            const uint64_t* point, uint64_t* comms_out, uint64_t* T_out, uint64_t* v_out,
+                            tpst_open_proof* proof);
+int tpst_pst_verify_combined(tpst_ctx* ctx, tpst_transcript* tr, int n, const uint64_t* point, const uint64_t* vs,
+                             const uint64_t* const* Ts, size_t B, const uint64_t* w, const tpst_open_proof* proof);
+
 /* ---- MultilinearPC single calls (ark-poly-commit fork) --
  * Against the loaded SRS; a polynomial of nv <= ck.nv variables uses level
  * ck.nv - nv.  evals: 2^nv canonical Fr (to_evaluations order); point: nv Fr,

@@ -90,6 +90,14 @@ PROTOTYPES = [
     ("tpst_poly_open_sharded", C.c_int, [_vp, _vp, _vp, C.c_int, _u64p, _u64p, _u64p, _vp, _vp]),
     ("tpst_pst_verify", C.c_int, [_vp, _vp, C.c_int, _u64p, _u64p, _u64p, _vp]),
     ("tpst_pst_verify_batch", C.c_int, [_vp, C.c_int, _vp, _sz, _u64p, C.POINTER(C.c_uint8)]),
+    ("tpst_poly_lincomb", C.c_int, [_vp, C.POINTER(_vp), _sz, _u64p, C.POINTER(_vp)]),
+    ("tpst_poly_evaluations", C.c_int, [_vp, _vp, _u64p]),
+    ("tpst_g1_lincomb_rows", C.c_int, [_vp, C.POINTER(_u64p), _sz, _sz, _u64p, _u64p]),
+    ("tpst_commit_lincomb", C.c_int, [_vp, C.c_int, C.POINTER(_u64p), C.POINTER(_u64p), _sz, _u64p, _u64p, _u64p]),
+    ("tpst_pst_combine_challenge", C.c_int, [_vp, C.c_int, _u64p, C.POINTER(_u64p), _u64p, _sz, _u64p]),
+    ("tpst_poly_open_combined", C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_u64p), C.POINTER(_u64p), _sz, _u64p, _vp,
+                                          _u64p, _u64p, _u64p, _u64p, _vp]),
+    ("tpst_pst_verify_combined", C.c_int, [_vp, _vp, C.c_int, _u64p, _u64p, C.POINTER(_u64p), _sz, _u64p, _vp]),
     ("tpst_mlpc_commit", C.c_int, [_vp, _u64p, C.c_int, _u64p]),
     ("tpst_mlpc_commit_g2", C.c_int, [_vp, _u64p, C.c_int, _u64p]),
     ("tpst_mlpc_open", C.c_int, [_vp, _u64p, C.c_int, _u64p, _u64p]),

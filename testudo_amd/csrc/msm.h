@@ -57,6 +57,8 @@ enum MsmStage {
   // lincomb.hip: k_lincomb2 launches (the batch verifier's and tpst_g*_lincomb_batch's);
   // tpst_pst_verify_batch: its multi-pairing call (G2 preparation to the final exponentiation) and its GT powers
   ST_LINCOMB, ST_VERIFY_BATCH_PAIRING, ST_VERIFY_BATCH_GT_POW,
+  // poly_lincomb.hip: k_fr_lincomb (tpst_poly_lincomb); k_g1_lincomb_rows and the sum of its chains
+  ST_FR_LINCOMB, ST_LINCOMB_ROWS,
   N_STAGES
 };
 

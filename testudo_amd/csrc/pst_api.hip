@@ -37,11 +37,6 @@ bool all_zero(const uint64_t* a, int n) {
     if (a[i]) return false;
   return true;
 }
-bool gt_ok(const uint64_t* f) {
-  for (int k = 0; k < 12; k++)
-    if (!fq_ok(f + 6 * k)) return false;
-  return true;
-}
 
 }  // namespace
 

@@ -39,6 +39,11 @@ inline bool limbs_lt(const uint64_t* a, const uint32_t* mod32, int n64) {
 }
 inline bool fq_ok(const uint64_t* a) { return limbs_lt(a, params::FQ_P, 6); }
 inline bool fr_ok(const uint64_t* a) { return limbs_lt(a, params::FR_P, 4); }
+inline bool gt_ok(const uint64_t* f) {  // the 12 Fq coefficients of a GT value
+  for (int k = 0; k < 12; k++)
+    if (!fq_ok(f + 6 * k)) return false;
+  return true;
+}
 
 // y > -y on canonical limbs  <=>  2y > p
 inline bool y_is_negative(const uint64_t* y) {
@@ -205,6 +210,21 @@ inline const uint32_t* poly_evals(const tpst_poly* p) { return p && !p->ncols ? 
 template <class F>
 inline bool point_valid(const uint64_t* p) {
   return host::point_in_subgroup<F>(p);
+}
+// canonical coordinates and on the curve (infinity = all-zero is on it), no
+// subgroup test: what the lincomb entry points ask of their points, as tpst_g1_msm
+template <class F>
+inline bool point_on_curve(const uint64_t* p) {
+  using H = typename host::HostOf<F>::T;
+  constexpr int NQ = host::HostOf<F>::NQ;
+  bool all0 = true;
+  for (int k = 0; k < 2 * NQ; k++) {
+    if (!fq_ok(p + 6 * k)) return false;
+    for (int i = 0; i < 6; i++) all0 = all0 && !p[6 * k + i];
+  }
+  if (all0) return true;
+  const Affine<H> a = host::aff_in<H>(p);
+  return eq(sqr(a.y), add(mul(sqr(a.x), a.x), CurveB<H>::b()));
 }
 
 }  // namespace tpst

@@ -45,12 +45,6 @@ using namespace tpst;
 
 namespace {
 
-bool gt_ok(const uint64_t* f) {
-  for (int k = 0; k < 12; k++)
-    if (!fq_ok(f + 6 * k)) return false;
-  return true;
-}
-
 // (x, -y) of a canonical affine point (NQ Fq coefficients per coordinate); infinity stays all-zero
 template <int NQ>
 void neg_point(const uint64_t* p, uint64_t* o) {

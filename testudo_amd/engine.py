@@ -143,7 +143,9 @@ class Context:
               # point_codec.hip: batched point decompression / validation
               "point_codec",
               # k_lincomb2 launches; tpst_pst_verify_batch's multi-pairing call and its GT powers
-              "lincomb", "verify_batch_pairing", "verify_batch_gt_pow")
+              "lincomb", "verify_batch_pairing", "verify_batch_gt_pow",
+              # poly_lincomb.hip: k_fr_lincomb; k_g1_lincomb_rows and the sum of its chains
+              "fr_lincomb", "lincomb_rows")
 
     def profile(self, on: bool):
         self.check(self.lib.tpst_profile_enable(self.h, 1 if on else 0), "tpst_profile_enable")

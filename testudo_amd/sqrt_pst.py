@@ -317,6 +317,27 @@ class Polynomial:
         self.ctx.check(self.ctx.lib.tpst_poly_commit_dev(self.ctx.h, self.h, C.c_void_p(d_comms),
                                                          C.c_void_p(d_T)), "commit_dev")
 
+    @classmethod
+    def lincomb(cls, polys, w) -> "Polynomial":
+        """tpst_poly_lincomb: Z* = sum_j w_j Z_j on the device, a new whole
+        Polynomial.  ``polys``: Polynomials of one context and one n; ``w``:
+        (B, 4) canonical Fr."""
+        polys = list(polys)
+        if not polys:
+            raise TpstError("lincomb needs at least one polynomial")
+        ctx = polys[0].ctx
+        w = _u64(w, (len(polys), 4))
+        hs = (C.c_void_p * len(polys))(*[p.h for p in polys])
+        h = C.c_void_p()
+        ctx.check(ctx.lib.tpst_poly_lincomb(ctx.h, hs, len(polys), ptr(w), C.byref(h)), "poly_lincomb")
+        return cls(ctx, h, polys[0].n)
+
+    def evaluations(self) -> np.ndarray:
+        """tpst_poly_evaluations: the (2^n, 4) canonical Fr of a whole polynomial."""
+        out = np.zeros((1 << self.n, 4), dtype=np.uint64)
+        self.ctx.check(self.ctx.lib.tpst_poly_evaluations(self.ctx.h, self.h, ptr(out)), "evaluations")
+        return out
+
     def open(self, transcript: PoseidonTranscript, comm_list, point, T):
         """sqrt_pst.rs:168-230 -> (U, pst_proof (m_row, 24), MippProof)."""
         comm_list = _u64(comm_list, (1 << self.m_col, 12))
@@ -500,6 +521,97 @@ def verify_batch(ctx: Context, items, rho=None):
         return False, ok
     ctx.check(rc, "verify_batch")
     return True, ok
+
+
+def _ptr_array(arrs):
+    """u64 arrays -> a ctypes array of their pointers (keep ``arrs`` alive for the call)."""
+    return (C.POINTER(C.c_uint64) * len(arrs))(*[ptr(a) for a in arrs])
+
+
+def g1_lincomb_rows(ctx: Context, lists, w) -> np.ndarray:
+    """tpst_g1_lincomb_rows: out[i] = sum_j w_j lists[j][i]; ``lists``: B
+    arrays of (C, 12) canonical affine G1, ``w``: (B, 4) Fr -> (C, 12)."""
+    lists = [_u64(x).reshape(-1, 12) for x in lists]
+    B = len(lists)
+    Cn = len(lists[0]) if B else 0
+    if any(len(x) != Cn for x in lists):
+        raise TpstError("lists of one combination share their length")
+    w = _u64(w, (B, 4)) if B else np.zeros((1, 4), dtype=np.uint64)
+    out = np.zeros((max(Cn, 1), 12), dtype=np.uint64)
+    ctx.check(ctx.lib.tpst_g1_lincomb_rows(ctx.h, _ptr_array(lists), B, Cn, ptr(w), ptr(out)), "g1_lincomb_rows")
+    return out[:Cn]
+
+
+def commit_lincomb(ctx: Context, n: int, comm_lists, Ts, w):
+    """tpst_commit_lincomb: (comm_list*, T*) of the combination with weights
+    ``w``; ``comm_lists`` or ``Ts`` may be None (its output is then None)."""
+    B = len(comm_lists if comm_lists is not None else Ts)
+    w = _u64(w, (B, 4))
+    cl = [_u64(x, (1 << (n // 2), 12)) for x in comm_lists] if comm_lists is not None else None
+    tl = [_u64(x, (72,)) for x in Ts] if Ts is not None else None
+    comms = np.zeros((1 << (n // 2), 12), dtype=np.uint64) if cl is not None else None
+    T = np.zeros(72, dtype=np.uint64) if tl is not None else None
+    ctx.check(ctx.lib.tpst_commit_lincomb(ctx.h, n, _ptr_array(cl) if cl is not None else None,
+                                          _ptr_array(tl) if tl is not None else None, B, ptr(w),
+                                          ptr(comms) if cl is not None else None,
+                                          ptr(T) if tl is not None else None), "commit_lincomb")
+    return comms, T
+
+
+def combine_challenge(transcript: PoseidonTranscript, point, Ts, vs) -> np.ndarray:
+    """tpst_pst_combine_challenge: the Fiat-Shamir weights of a combined
+    opening, (B, 4) Fr with w_j = rho^j; ``transcript`` absorbs every T_j, the
+    point and every v_j and is squeezed once."""
+    point = _u64(point).reshape(-1, 4)
+    tl = [_u64(x, (72,)) for x in Ts]
+    vs = _u64(vs, (len(tl), 4))
+    w = np.zeros((len(tl), 4), dtype=np.uint64)
+    rc = transcript.lib.tpst_pst_combine_challenge(C.byref(transcript.t), len(point), ptr(point), _ptr_array(tl),
+                                                   ptr(vs), len(tl), ptr(w))
+    if rc:
+        raise TpstError("combine_challenge: rc=%d" % rc)
+    return w
+
+
+def open_combined(polys, commitments, transcript: PoseidonTranscript, point, w=None):
+    """tpst_poly_open_combined: one opening for B polynomials at ``point``.
+    ``commitments``: their (comm_list, T) pairs.  ``w`` None: every polynomial
+    is evaluated and the weights come from ``combine_challenge`` on
+    ``transcript`` (the verifier repeats that call).  Returns (w, comm_list*,
+    T*, v*, (U, pst_proof, MippProof))."""
+    polys = list(polys)
+    ctx, n, B = polys[0].ctx, polys[0].n, len(polys)
+    point = _u64(point, (n, 4))
+    cl = [_u64(c, (1 << (n // 2), 12)) for c, _ in commitments]
+    tl = [_u64(T, (72,)) for _, T in commitments]
+    if w is None:
+        w = combine_challenge(transcript, point, tl, np.stack([p.eval(point) for p in polys]))
+    w = _u64(w, (B, 4))
+    hs = (C.c_void_p * B)(*[p.h for p in polys])
+    comms = np.zeros((1 << (n // 2), 12), dtype=np.uint64)
+    T, v = np.zeros(72, dtype=np.uint64), np.zeros(4, dtype=np.uint64)
+    pr = _lib.OpenProof()
+    ctx.check(ctx.lib.tpst_poly_open_combined(ctx.h, hs, _ptr_array(cl), _ptr_array(tl), B, ptr(w),
+                                              C.byref(transcript.t), ptr(point), ptr(comms), ptr(T), ptr(v),
+                                              C.byref(pr)), "open_combined")
+    return w, comms, T, v, _unpack(pr)
+
+
+def verify_combined(ctx: Context, transcript: PoseidonTranscript, U, point, vs, pst_proof, mipp: MippProof, Ts,
+                    w) -> bool:
+    """tpst_pst_verify_combined: ``verify`` of one combined opening against
+    the B commitments ``Ts`` and claimed values ``vs`` under the weights ``w``."""
+    point = _u64(point).reshape(-1, 4)
+    n = len(point)
+    tl = [_u64(x, (72,)) for x in Ts]
+    B = len(tl)
+    pr = pack_proof(n, U, pst_proof, mipp)
+    rc = ctx.lib.tpst_pst_verify_combined(ctx.h, C.byref(transcript.t), n, ptr(point), ptr(_u64(vs, (B, 4))),
+                                          _ptr_array(tl), B, ptr(_u64(w, (B, 4))), C.byref(pr))
+    if rc == -5:
+        return False
+    ctx.check(rc, "verify_combined")
+    return True
 
 
 def g1_msm_partial_into(ctx: Context, d_bases: int, d_scalars: int, i0: int, i1: int, out) -> None:

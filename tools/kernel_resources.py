@@ -64,6 +64,10 @@ HOT = [
     # the batch verifier's G1 double-scalar chains (lincomb.hip); the G2 form parks ~30 VGPRs in AGPRs (no
     # scratch), see profiles/verify_batch/README.md
     "k_lincomb2<Fp<FqCfg> >",
+    # the combined opening's table and row combinations (poly_lincomb.hip)
+    "k_fr_lincomb",
+    "k_g1_lincomb_rows",
+    "k_g1_rows_sum",
 ]
 
 FIELDS = {
@@ -142,7 +146,8 @@ def main() -> int:
     text = "\n".join(lines) + "\n"
     seen = {short(r["name"]) for r in rows}
     # every file with a HOT kernel (msm.hip: K2; msm_batch.hip: K1 and the reductions both use)
-    whole = not a.only or {"msm.hip", "msm_batch.hip", "hyrax.hip", "product_tree.hip", "lincomb.hip"} <= set(a.only.split(","))
+    whole = not a.only or {"msm.hip", "msm_batch.hip", "hyrax.hip", "product_tree.hip", "lincomb.hip",
+                                "poly_lincomb.hip"} <= set(a.only.split(","))
     missing = [h for h in HOT if h not in seen] if whole else []
     if missing:
         text += "\nHOT kernels not found (renamed?):\n" + "\n".join("  " + m for m in missing) + "\n"
