@@ -429,6 +429,85 @@ int tpst_poly_open_combined(tpst_ctx* ctx, tpst_poly* const* polys, const uint64
 int tpst_pst_verify_combined(tpst_ctx* ctx, tpst_transcript* tr, int n, const uint64_t* point, const uint64_t* vs,
                              const uint64_t* const* Ts, size_t B, const uint64_t* w, const tpst_open_proof* proof);
 
+/* Multi-point opening: B polynomials of the same n (1 <= B <= 256), committed
+ * one by one, opened at MANY points with ONE proof: K claims (1 <= K <= 4096)
+ *   f_{j_k}(r_k) = v_k,  k < K,  j_k < B,  r_k in Fr^n,
+ * every polynomial in at least one claim; a polynomial may occur in several
+ * claims and a point may repeat.  This protocol is this library's own: the
+ * reference has no counterpart.  Points and tables are in tpst_poly_eval's
+ * order (v = sum_x Z[x] eq(r, x), r[0] the most significant bit of x).
+ *
+ * A sum-check reduces the K claims to B claims at one random point rho, which
+ * one combined opening (above) then proves.  On the caller's transcript,
+ * prover and verifier alike:
+ *  1. statement: tpst_transcript_append_fr of B, K and n (the Fr of each
+ *     integer); append_gt of T_0..T_{B-1}; per claim in order append_fr of
+ *     j_k, of the n coordinates of r_k and of v_k; one challenge gamma;
+ *     a_k = gamma^k (a_0 = 1).
+ *  2. sum-check of e_0 = sum_k a_k v_k over g(x) = sum_j D_j(x) f_j(x) with
+ *     D_j(x) = sum_{k: j_k = j} a_k eq(r_k, x): n rounds, round i binds
+ *     variable i (the most significant first).  The round polynomial s_i has
+ *     s_i(0) + s_i(1) = e_i; its coefficients c0, c1, c2 (UniPoly::from_evals
+ *     of s_i(0), s_i(1), s_i(2), constant first) are the proof's and are
+ *     absorbed with append_fr; one challenge rho_i; e_{i+1} = s_i(rho_i).
+ *  3. final values: the proof carries u_j = f_j(rho); the check is
+ *     e_n = sum_j u_j D_j(rho),
+ *     D_j(rho) = sum_{k: j_k = j} a_k prod_i (r_ki rho_i + (1 - r_ki)(1 - rho_i)).
+ *  4. tpst_pst_combine_challenge(tr, n, rho, Ts, u) gives the weights w of the
+ *     combined opening of all B polynomials at rho with values u.
+ * The proof: the n x 3 round coefficients, the B values u_j, one
+ * tpst_open_proof.  Its wire format, a sharded (multi-rank) form and merging
+ * claims that share a point are not part of this interface.
+ *
+ * SOUNDNESS: the sum-check bound (2n / r) plus the two random linear
+ * combinations ((K - 1) / r and (B - 1) / r).  IT HOLDS ONLY BECAUSE gamma IS
+ * DRAWN AFTER EVERY T_j, EVERY POINT AND EVERY CLAIMED VALUE ARE ABSORBED, AND
+ * THE WEIGHTS OF STEP 4 AFTER EVERY u_j: a caller that replays these steps
+ * itself must keep that order, and whatever fixed the commitments must be on
+ * the transcript before the call.  With a gamma the prover can predict, wrong
+ * values can be made to cancel in e_0.
+ *
+ * Claim k is (claim_poly[k], points + 4 n k, vals + 4 k); rounds is n x 3 Fr,
+ * u B Fr, rho n Fr.
+ *
+ * tpst_poly_open_multi: the prover.  Steps 1-3 with the reduction on the
+ *   device (the handles' tables are read, never written), then step 4 and
+ *   tpst_poly_open_combined at rho; writes rounds, u, rho and what that call
+ *   writes (comm_list*, T*, v*, the proof).  tr ends as tpst_poly_open_combined
+ *   at rho leaves it, and is unchanged on any error.  THE PROVER DOES NOT CHECK
+ *   THAT v_k IS RIGHT: a wrong claim yields a proof the verifier rejects.
+ *   TPST_E_ARG: a null argument, B = 0, K = 0, B > 256, K > 4096, an index
+ *   >= B, a polynomial with no claim, polynomials of different n or of another
+ *   context, a coordinate or value >= r.  TPST_E_STATE: a handle that is not a
+ *   whole polynomial, no SRS loaded.
+ * tpst_pst_multi_reduce: HOST ONLY, no context: the verifier's steps 1-3.  On
+ *   TPST_OK rho is written and tr stands where step 4 starts.  TPST_E_VERIFY: a
+ *   failed round check or final identity, or any scalar (coordinate, value,
+ *   round coefficient, u_j) >= r or T_j coefficient >= p.  TPST_E_ARG: misuse
+ *   (null argument, bad n, B or K out of range, an index >= B, a polynomial
+ *   with no claim).  tr is unchanged on any failure.
+ * tpst_pst_verify_multi: tpst_pst_multi_reduce, tpst_pst_combine_challenge,
+ *   tpst_pst_verify_combined.  TPST_OK or TPST_E_VERIFY; TPST_E_ARG also for
+ *   sizes that do not match n; TPST_E_STATE: no SRS loaded.  tr is changed only
+ *   on TPST_OK.
+ * tpst_poly_multi_sumcheck_stages: test entry.  The device reduction alone --
+ *   the prover's own round loop -- with the caller's weights a (K Fr, zero
+ *   allowed) and challenges rho (n Fr): sums = n x 2 Fr, s_i(0) and s_i(2) of
+ *   every round; u as above.  Errors as tpst_poly_open_multi (no SRS needed). */
+int tpst_poly_open_multi(tpst_ctx* ctx, tpst_poly* const* polys, const uint64_t* const* comms,
+                         const uint64_t* const* Ts, size_t B, const uint32_t* claim_poly, const uint64_t* points,
+                         const uint64_t* vals, size_t K, tpst_transcript* tr, uint64_t* rounds, uint64_t* u,
+                         uint64_t* rho, uint64_t* comms_out, uint64_t* T_out, uint64_t* v_out, tpst_open_proof* proof);
+int tpst_pst_multi_reduce(tpst_transcript* tr, int n, const uint64_t* const* Ts, size_t B, const uint32_t* claim_poly,
+                          const uint64_t* points, const uint64_t* vals, size_t K, const uint64_t* rounds,
+                          const uint64_t* u, uint64_t* rho);
+int tpst_pst_verify_multi(tpst_ctx* ctx, tpst_transcript* tr, int n, const uint64_t* const* Ts, size_t B,
+                          const uint32_t* claim_poly, const uint64_t* points, const uint64_t* vals, size_t K,
+                          const uint64_t* rounds, const uint64_t* u, const tpst_open_proof* proof);
+int tpst_poly_multi_sumcheck_stages(tpst_ctx* ctx, tpst_poly* const* polys, size_t B, const uint32_t* claim_poly,
+                                    const uint64_t* points, const uint64_t* a, size_t K, const uint64_t* rho,
+                                    uint64_t* sums, uint64_t* u);
+
 /* ---- MultilinearPC single calls (ark-poly-commit fork) --
  * Against the loaded SRS; a polynomial of nv <= ck.nv variables uses level
  * ck.nv - nv.  evals: 2^nv canonical Fr (to_evaluations order); point: nv Fr,

@@ -98,6 +98,15 @@ PROTOTYPES = [
     ("tpst_poly_open_combined", C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_u64p), C.POINTER(_u64p), _sz, _u64p, _vp,
                                           _u64p, _u64p, _u64p, _u64p, _vp]),
     ("tpst_pst_verify_combined", C.c_int, [_vp, _vp, C.c_int, _u64p, _u64p, C.POINTER(_u64p), _sz, _u64p, _vp]),
+    ("tpst_poly_open_multi", C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_u64p), C.POINTER(_u64p), _sz,
+                                       C.POINTER(C.c_uint32), _u64p, _u64p, _sz, _vp, _u64p, _u64p, _u64p, _u64p, _u64p,
+                                       _u64p, _vp]),
+    ("tpst_pst_multi_reduce", C.c_int, [_vp, C.c_int, C.POINTER(_u64p), _sz, C.POINTER(C.c_uint32), _u64p, _u64p, _sz,
+                                        _u64p, _u64p, _u64p]),
+    ("tpst_pst_verify_multi", C.c_int, [_vp, _vp, C.c_int, C.POINTER(_u64p), _sz, C.POINTER(C.c_uint32), _u64p, _u64p,
+                                        _sz, _u64p, _u64p, _vp]),
+    ("tpst_poly_multi_sumcheck_stages", C.c_int, [_vp, C.POINTER(_vp), _sz, C.POINTER(C.c_uint32), _u64p, _u64p, _sz,
+                                                  _u64p, _u64p, _u64p]),
     ("tpst_mlpc_commit", C.c_int, [_vp, _u64p, C.c_int, _u64p]),
     ("tpst_mlpc_commit_g2", C.c_int, [_vp, _u64p, C.c_int, _u64p]),
     ("tpst_mlpc_open", C.c_int, [_vp, _u64p, C.c_int, _u64p, _u64p]),

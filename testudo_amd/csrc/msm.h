@@ -59,6 +59,9 @@ enum MsmStage {
   ST_LINCOMB, ST_VERIFY_BATCH_PAIRING, ST_VERIFY_BATCH_GT_POW,
   // poly_lincomb.hip: k_fr_lincomb (tpst_poly_lincomb); k_g1_lincomb_rows and the sum of its chains
   ST_FR_LINCOMB, ST_LINCOMB_ROWS,
+  // poly_multi.hip, the multi-point reduction (round kernel + reduce launch): round 0 (reads the handles); round 1
+  // (binds from the handles, writes the scratch tables); every later round and the closing bind
+  ST_MULTI_ROUND0, ST_MULTI_ROUND1, ST_MULTI_ROUNDS,
   N_STAGES
 };
 

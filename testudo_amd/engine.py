@@ -145,7 +145,9 @@ class Context:
               # k_lincomb2 launches; tpst_pst_verify_batch's multi-pairing call and its GT powers
               "lincomb", "verify_batch_pairing", "verify_batch_gt_pow",
               # poly_lincomb.hip: k_fr_lincomb; k_g1_lincomb_rows and the sum of its chains
-              "fr_lincomb", "lincomb_rows")
+              "fr_lincomb", "lincomb_rows",
+              # poly_multi.hip: round 0, round 1, and the later rounds with the closing bind of the multi-point reduction
+              "multi_round0", "multi_round1", "multi_rounds")
 
     def profile(self, on: bool):
         self.check(self.lib.tpst_profile_enable(self.h, 1 if on else 0), "tpst_profile_enable")

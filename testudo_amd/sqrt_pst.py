@@ -614,6 +614,111 @@ def verify_combined(ctx: Context, transcript: PoseidonTranscript, U, point, vs, 
     return True
 
 
+@dataclass
+class MultiOpenProof:
+    """The proof of a multi-point opening (include/tpst.h): the sum-check's
+    round coefficients, the B values at rho and one opening."""
+    rounds: np.ndarray       # (n, 3, 4) Fr: c0, c1, c2 of every round
+    u: np.ndarray            # (B, 4) Fr: u_j = f_j(rho)
+    U: np.ndarray            # (12,)
+    pst_proof: np.ndarray    # (m_row, 24)
+    mipp: MippProof
+
+
+def _claims(claims, n):
+    """[(poly_index, point, value)] -> the three arrays of the C-ABI (kept alive by the caller)"""
+    claims = list(claims)
+    if not claims:
+        raise TpstError("a multi-point opening needs at least one claim")
+    for j, _, _ in claims:
+        if int(j) < 0 or int(j) >= 2**32:
+            raise TpstError("claim on a polynomial index out of range")
+    idx = np.ascontiguousarray([int(j) for j, _, _ in claims], dtype=np.uint32)
+    pts = np.ascontiguousarray(np.stack([_u64(p, (n, 4)) for _, p, _ in claims]))
+    vals = np.ascontiguousarray(np.stack([_u64(v, (4,)) for _, _, v in claims]))
+    return idx, pts, vals
+
+
+def _u32p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
+def open_multi(polys, commitments, transcript: PoseidonTranscript, claims):
+    """tpst_poly_open_multi: one proof for K claims (poly_index, point, value)
+    on B committed polynomials of one size; ``commitments``: their (comm_list,
+    T) pairs.  The values are not checked: a wrong one yields a proof that
+    ``verify_multi`` rejects.  Returns (MultiOpenProof, rho (n, 4), comm_list*,
+    T*, v*); the last three are what ``open_combined`` at rho returns."""
+    polys = list(polys)
+    ctx, n, B = polys[0].ctx, polys[0].n, len(polys)
+    idx, pts, vals = _claims(claims, n)
+    cl = [_u64(c, (1 << (n // 2), 12)) for c, _ in commitments]
+    tl = [_u64(T, (72,)) for _, T in commitments]
+    hs = (C.c_void_p * B)(*[p.h for p in polys])
+    rounds = np.zeros((n, 3, 4), dtype=np.uint64)
+    u, rho = np.zeros((B, 4), dtype=np.uint64), np.zeros((n, 4), dtype=np.uint64)
+    comms = np.zeros((1 << (n // 2), 12), dtype=np.uint64)
+    T, v = np.zeros(72, dtype=np.uint64), np.zeros(4, dtype=np.uint64)
+    pr = _lib.OpenProof()
+    ctx.check(ctx.lib.tpst_poly_open_multi(ctx.h, hs, _ptr_array(cl), _ptr_array(tl), B, _u32p(idx), ptr(pts),
+                                           ptr(vals), len(idx), C.byref(transcript.t), ptr(rounds), ptr(u), ptr(rho),
+                                           ptr(comms), ptr(T), ptr(v), C.byref(pr)), "open_multi")
+    U, pst_proof, mipp = _unpack(pr)
+    return MultiOpenProof(rounds, u, U, pst_proof, mipp), rho, comms, T, v
+
+
+def multi_reduce(transcript: PoseidonTranscript, n: int, claims, Ts, rounds, u):
+    """tpst_pst_multi_reduce (host only): the verifier's statement absorb,
+    round checks and final identity.  Returns rho (n, 4) with ``transcript``
+    where the combined opening starts, or None (transcript unchanged) when a
+    check fails; misuse raises."""
+    idx, pts, vals = _claims(claims, n)
+    tl = [_u64(x, (72,)) for x in Ts]
+    B = len(tl)
+    rho = np.zeros((n, 4), dtype=np.uint64)
+    rc = transcript.lib.tpst_pst_multi_reduce(C.byref(transcript.t), n, _ptr_array(tl), B, _u32p(idx), ptr(pts),
+                                              ptr(vals), len(idx), ptr(_u64(rounds, (n, 3, 4))), ptr(_u64(u, (B, 4))),
+                                              ptr(rho))
+    if rc == -5:
+        return None
+    if rc:
+        raise TpstError("multi_reduce: rc=%d" % rc)
+    return rho
+
+
+def verify_multi(ctx: Context, transcript: PoseidonTranscript, claims, Ts, proof: MultiOpenProof) -> bool:
+    """tpst_pst_verify_multi: the K claims (poly_index, point, value) against
+    the B commitments ``Ts`` and one MultiOpenProof."""
+    n = len(proof.rounds)
+    idx, pts, vals = _claims(claims, n)
+    tl = [_u64(x, (72,)) for x in Ts]
+    B = len(tl)
+    pr = pack_proof(n, proof.U, proof.pst_proof, proof.mipp)
+    rc = ctx.lib.tpst_pst_verify_multi(ctx.h, C.byref(transcript.t), n, _ptr_array(tl), B, _u32p(idx), ptr(pts),
+                                       ptr(vals), len(idx), ptr(_u64(proof.rounds, (n, 3, 4))),
+                                       ptr(_u64(proof.u, (B, 4))), C.byref(pr))
+    if rc == -5:
+        return False
+    ctx.check(rc, "verify_multi")
+    return True
+
+
+def multi_sumcheck_stages(polys, claims, a, rho):
+    """tpst_poly_multi_sumcheck_stages (test entry): the device reduction
+    alone under the caller's weights ``a`` (K, 4) and challenges ``rho`` (n,
+    4); the claims' values are not used.  Returns (sums (n, 2, 4): s_i(0) and
+    s_i(2), u (B, 4))."""
+    polys = list(polys)
+    ctx, n, B = polys[0].ctx, polys[0].n, len(polys)
+    idx, pts, _ = _claims(claims, n)
+    hs = (C.c_void_p * B)(*[p.h for p in polys])
+    sums, u = np.zeros((n, 2, 4), dtype=np.uint64), np.zeros((B, 4), dtype=np.uint64)
+    ctx.check(ctx.lib.tpst_poly_multi_sumcheck_stages(ctx.h, hs, B, _u32p(idx), ptr(pts), ptr(_u64(a, (len(idx), 4))),
+                                                      len(idx), ptr(_u64(rho, (n, 4))), ptr(sums), ptr(u)),
+              "multi_sumcheck_stages")
+    return sums, u
+
+
 def g1_msm_partial_into(ctx: Context, d_bases: int, d_scalars: int, i0: int, i1: int, out) -> None:
     """Points [i0, i1) of a device-resident MSM (Montgomery bases, canonical Fr
     scalars) summed into the int64 tensor ``out`` (24 words, raw XYZZ; a host

@@ -68,6 +68,12 @@ HOT = [
     "k_fr_lincomb",
     "k_g1_lincomb_rows",
     "k_g1_rows_sum",
+    # the multi-point opening's reduction (poly_multi.hip)
+    "k_multi_eq_halves",
+    "k_multi_round<0>",
+    "k_multi_round<1>",
+    "k_multi_round<2>",
+    "k_multi_reduce",
 ]
 
 FIELDS = {
