@@ -508,6 +508,102 @@ int tpst_poly_multi_sumcheck_stages(tpst_ctx* ctx, tpst_poly* const* polys, size
                                     const uint64_t* points, const uint64_t* a, size_t K, const uint64_t* rho,
                                     uint64_t* sums, uint64_t* u);
 
+/* Product sum-check: a relation between B committed polynomials of the same n
+ * (1 <= B <= 256), each committed on its own as (comm_list_j, T_j), proved by
+ * a sum-check over a sum of products of their tables and ONE combined opening.
+ * M terms (1 <= M <= 64); term t is (deg_t in {1, 2, 3}, idx_t[0..deg_t) < B,
+ * c_t in Fr).  An index may repeat inside a term (f f, f f f), every polynomial
+ * occurs in at least one term, c_t = 0 is allowed.  With
+ *   g(x) = sum_t c_t prod_{i < deg_t} f_{idx_t[i]}(x)
+ * and an optional point tau in Fr^n the claim is
+ *   e_0 = sum_{x in {0,1}^n} eq(tau, x) g(x)      (without tau: sum_x g(x)).
+ * a o b = c is g = f_0 f_1 - f_2 with tau and e_0 = 0; sum a b = s is
+ * g = f_0 f_1; sum a b c = s is g = f_0 f_1 f_2.  Points and tables are in
+ * tpst_poly_eval's order, tau[0] the most significant bit of x.  The round
+ * degree is D = max_t deg_t + (tau given ? 1 : 0); D > 3 is TPST_E_ARG and
+ * D = 1 is run as D = 2 (UniPoly::from_evals takes 3 or 4 evaluations).  This
+ * protocol is this library's own: the reference's sum-checks are private to
+ * R1CSProof and the product tree.
+ *
+ * On the caller's transcript, prover and verifier alike:
+ *  1. statement: tpst_transcript_append_fr of B, M, n and has_tau (0 or 1),
+ *     each as the Fr of the integer; append_gt of T_0..T_{B-1}; per term in
+ *     order append_fr of deg_t, of each of its deg_t indices and of c_t; the n
+ *     coordinates of tau, if given; append_fr of e_0.
+ *  2. rounds: n rounds, round i binds variable i (the most significant
+ *     first).  The round polynomial s_i has degree <= D and
+ *     s_i(0) + s_i(1) = e_i; its D + 1 coefficients (UniPoly::from_evals of
+ *     s_i(0..D), constant first) are the proof's and are absorbed with
+ *     append_fr; one challenge rho_i; e_{i+1} = s_i(rho_i).
+ *  3. final values: the proof carries u_j = f_j(rho); the check is
+ *     e_n = [prod_i (tau_i rho_i + (1 - tau_i)(1 - rho_i))]
+ *           sum_t c_t prod_i u_{idx_t[i]}       (the bracket only with tau).
+ *  4. tpst_pst_combine_challenge(tr, n, rho, Ts, u) gives the weights w of the
+ *     combined opening of all B polynomials at rho with values u.
+ * The proof: the n x (D + 1) round coefficients, the B values u_j, one
+ * tpst_open_proof.  Its wire format, a sharded (multi-rank) form, degrees
+ * above 3 and terms over polynomials of different n are not part of this
+ * interface.
+ *
+ * SOUNDNESS: the sum-check bound (D n / r) plus the combination ((B - 1) / r).
+ * IT HOLDS ONLY BECAUSE EVERY T_j, EVERY TERM, tau AND e_0 ARE ABSORBED BEFORE
+ * rho_0 IS DRAWN, AND THE WEIGHTS OF STEP 4 AFTER EVERY u_j: a caller that
+ * replays these steps itself must keep that order, and whatever fixed the
+ * commitments must be on the transcript before the call.  A tau MEANT AS
+ * ZERO-CHECK RANDOMNESS (a o b = c for every x, not just under one weighting)
+ * MUST BE DRAWN BY THE CALLER AFTER THE COMMITMENTS ARE FIXED, e.g. squeezed
+ * from the transcript once every T_j is on it: that is the caller's protocol,
+ * not this call's, which takes tau as part of the statement.
+ *
+ * terms: M tpst_sc_term (idx entries past deg are ignored); tau: n Fr or NULL;
+ * rounds is n x (D + 1) Fr, u B Fr, rho n Fr, e0 one Fr.
+ *
+ * tpst_poly_sumcheck_open: the prover.  e_0 is an OUTPUT: round 0 computes
+ *   s_0(0) and s_0(1) on the device and their sum is the claim; the statement
+ *   is absorbed once that is known.  Then steps 2-3 with the rounds on the
+ *   device (the handles' tables are read, never written), step 4 and
+ *   tpst_poly_open_combined at rho; writes e0, rounds, u, rho and what that
+ *   call writes (comm_list*, T*, v*, the proof).  tr ends as
+ *   tpst_poly_open_combined at rho leaves it, and is unchanged on any error.
+ *   TPST_E_ARG: a null argument (tau may be NULL), B, M or a degree out of
+ *   range, D > 3, an index >= B, a polynomial in no term, polynomials of
+ *   different n or of another context, a coefficient or coordinate >= r.
+ *   TPST_E_STATE: a handle that is not a whole polynomial, no SRS loaded.
+ * tpst_pst_sumcheck_reduce: HOST ONLY, no context: the verifier's steps 1-3 on
+ *   a claimed e_0.  On TPST_OK rho is written and tr stands where step 4
+ *   starts.  TPST_E_VERIFY: a failed round check or final identity, or any
+ *   scalar (coefficient, coordinate, e_0, round coefficient, u_j) >= r or T_j
+ *   coefficient >= p.  TPST_E_ARG: misuse (null argument, bad n, B, M or a
+ *   degree out of range, D > 3, an index >= B, a polynomial in no term).  tr is
+ *   unchanged on any failure.
+ * tpst_pst_verify_sumcheck: tpst_pst_sumcheck_reduce,
+ *   tpst_pst_combine_challenge, tpst_pst_verify_combined.  TPST_OK or
+ *   TPST_E_VERIFY; TPST_E_ARG also for sizes that do not match n;
+ *   TPST_E_STATE: no SRS loaded.  tr is changed only on TPST_OK.
+ * tpst_poly_sumcheck_stages: test entry.  The device rounds alone -- the
+ *   prover's own loop -- on the caller's challenges rho (n Fr): sums =
+ *   n x (D + 1) Fr, s_i(0..D) of every round (s_i(1) of a round after the
+ *   first is e_i - s_i(0), as the prover takes it); u as above.  Errors as
+ *   tpst_poly_sumcheck_open (no SRS needed). */
+typedef struct tpst_sc_term {
+  uint32_t deg;      /* 1..3 */
+  uint32_t idx[3];   /* polynomial indices, the first deg are used */
+  uint64_t coeff[4]; /* c_t, canonical Fr */
+} tpst_sc_term;
+int tpst_poly_sumcheck_open(tpst_ctx* ctx, tpst_poly* const* polys, const uint64_t* const* comms,
+                            const uint64_t* const* Ts, size_t B, const tpst_sc_term* terms, size_t M,
+                            const uint64_t* tau, tpst_transcript* tr, uint64_t* e0, uint64_t* rounds, uint64_t* u,
+                            uint64_t* rho, uint64_t* comms_out, uint64_t* T_out, uint64_t* v_out,
+                            tpst_open_proof* proof);
+int tpst_pst_sumcheck_reduce(tpst_transcript* tr, int n, const uint64_t* const* Ts, size_t B, const tpst_sc_term* terms,
+                             size_t M, const uint64_t* tau, const uint64_t* e0, const uint64_t* rounds,
+                             const uint64_t* u, uint64_t* rho);
+int tpst_pst_verify_sumcheck(tpst_ctx* ctx, tpst_transcript* tr, int n, const uint64_t* const* Ts, size_t B,
+                             const tpst_sc_term* terms, size_t M, const uint64_t* tau, const uint64_t* e0,
+                             const uint64_t* rounds, const uint64_t* u, const tpst_open_proof* proof);
+int tpst_poly_sumcheck_stages(tpst_ctx* ctx, tpst_poly* const* polys, size_t B, const tpst_sc_term* terms, size_t M,
+                              const uint64_t* tau, const uint64_t* rho, uint64_t* sums, uint64_t* u);
+
 /* ---- MultilinearPC single calls (ark-poly-commit fork) --
  * Against the loaded SRS; a polynomial of nv <= ck.nv variables uses level
  * ck.nv - nv.  evals: 2^nv canonical Fr (to_evaluations order); point: nv Fr,

@@ -107,6 +107,14 @@ PROTOTYPES = [
                                         _sz, _u64p, _u64p, _vp]),
     ("tpst_poly_multi_sumcheck_stages", C.c_int, [_vp, C.POINTER(_vp), _sz, C.POINTER(C.c_uint32), _u64p, _u64p, _sz,
                                                   _u64p, _u64p, _u64p]),
+    # terms: a (tpst_sc_term * M) array, handed over as void*
+    ("tpst_poly_sumcheck_open", C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_u64p), C.POINTER(_u64p), _sz, _vp, _sz, _u64p,
+                                          _vp, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p, _vp]),
+    ("tpst_pst_sumcheck_reduce", C.c_int, [_vp, C.c_int, C.POINTER(_u64p), _sz, _vp, _sz, _u64p, _u64p, _u64p, _u64p,
+                                           _u64p]),
+    ("tpst_pst_verify_sumcheck", C.c_int, [_vp, _vp, C.c_int, C.POINTER(_u64p), _sz, _vp, _sz, _u64p, _u64p, _u64p,
+                                           _u64p, _vp]),
+    ("tpst_poly_sumcheck_stages", C.c_int, [_vp, C.POINTER(_vp), _sz, _vp, _sz, _u64p, _u64p, _u64p, _u64p]),
     ("tpst_mlpc_commit", C.c_int, [_vp, _u64p, C.c_int, _u64p]),
     ("tpst_mlpc_commit_g2", C.c_int, [_vp, _u64p, C.c_int, _u64p]),
     ("tpst_mlpc_open", C.c_int, [_vp, _u64p, C.c_int, _u64p, _u64p]),
@@ -228,6 +236,11 @@ class OpenProof(C.Structure):
         ("final_h", C.c_uint64 * 24),
         ("pst_proof_h", (C.c_uint64 * 12) * MAX_VARS),
     ]
+
+class ScTerm(C.Structure):
+    """tpst_sc_term: one term c prod_i f_idx[i] of a product sum-check."""
+    _fields_ = [("deg", C.c_uint32), ("idx", C.c_uint32 * 3), ("coeff", C.c_uint64 * 4)]
+
 
 class VerifyItem(C.Structure):
     """tpst_verify_item: one opening of tpst_pst_verify_batch."""

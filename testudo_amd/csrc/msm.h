@@ -62,6 +62,9 @@ enum MsmStage {
   // poly_multi.hip, the multi-point reduction (round kernel + reduce launch): round 0 (reads the handles); round 1
   // (binds from the handles, writes the scratch tables); every later round and the closing bind
   ST_MULTI_ROUND0, ST_MULTI_ROUND1, ST_MULTI_ROUNDS,
+  // poly_sumcheck.hip, the product sum-check (round kernel + reduce launch): round 0 (reads the handles); round 1
+  // (binds from the handles, writes the scratch tables); every later round and the closing bind
+  ST_SC_ROUND0, ST_SC_ROUND1, ST_SC_ROUNDS,
   N_STAGES
 };
 

@@ -5,9 +5,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <functional>
+#include <vector>
 #include "msm.h"
 
 struct tpst_ctx;
+struct tpst_poly;
 
 namespace tpst {
 
@@ -53,5 +55,10 @@ hipError_t multi_round(hipStream_t s, int round, const MultiSrc& src, uint32_t* 
 using MultiChallenge = std::function<int(int round, const uint64_t* s0, const uint64_t* s2, uint64_t* rho)>;
 int multi_sumcheck(tpst_ctx* ctx, const uint32_t* const* tabs, size_t B, int n, const uint32_t* claim_poly,
                    const uint64_t* points, const uint64_t* a, size_t K, const MultiChallenge& challenge, uint64_t* u);
+
+// The device tables of B whole polynomials of one context and one n, read under the context's lock (also
+// poly_sumcheck.hip's).  TPST_E_ARG: a null handle, another context, differing n, a table not 16-byte aligned;
+// TPST_E_STATE: a column slice or q-only handle.
+int whole_tables(tpst_ctx* ctx, tpst_poly* const* polys, size_t B, std::vector<const uint32_t*>& tabs);
 
 }  // namespace tpst

@@ -38,6 +38,7 @@
 #include "../../include/tpst.h"
 #include "ctx.h"
 #include "device_util.h"
+#include "fr_mem.h"
 #include "poly_lincomb.h"
 #include "poly_multi.h"
 #include "poseidon_host.h"
@@ -51,20 +52,6 @@ namespace {
 constexpr int MP_BS = 256;
 // a few resident workgroups per CU keep the loads in flight; the stride loop covers the rest
 constexpr unsigned MP_MAX_GRID = 256 * 8;
-
-__device__ __forceinline__ Fr ld_fr16(const uint32_t* p) {
-  const uint4 a = reinterpret_cast<const uint4*>(p)[0], b = reinterpret_cast<const uint4*>(p)[1];
-  Fr r;
-  r.v[0] = a.x, r.v[1] = a.y, r.v[2] = a.z, r.v[3] = a.w;
-  r.v[4] = b.x, r.v[5] = b.y, r.v[6] = b.z, r.v[7] = b.w;
-  return r;
-}
-
-__device__ __forceinline__ void st_fr16(uint32_t* p, const Fr& a) {
-  uint4* o = reinterpret_cast<uint4*>(p);
-  o[0] = make_uint4(a.v[0], a.v[1], a.v[2], a.v[3]);
-  o[1] = make_uint4(a.v[4], a.v[5], a.v[6], a.v[7]);
-}
 
 // thread t < K (2^hi + 2^lo): entry i of claim c's high table (i < 2^hi) or of its low table
 __global__ void __launch_bounds__(MP_BS) k_multi_eq_halves(const uint32_t* __restrict__ pts,
@@ -95,9 +82,6 @@ __device__ __forceinline__ Fr d_at(const MultiSrc& s, uint32_t c0, uint32_t c1, 
     acc = add(acc, mul(ld_fr16(s.eh + 8 * (((size_t)c << s.hi) + xh)), ld_fr16(s.el + 8 * (((size_t)c << s.lo) + xl))));
   return acc;
 }
-
-// a + r (b - a): r Montgomery; a, b both Montgomery or both canonical, the result as they are
-__device__ __forceinline__ Fr bind_top(const Fr& r, const Fr& a, const Fr& b) { return add(a, mul(r, sub(b, a))); }
 
 // MODE 0: the tables (src) have length h, nothing is bound.
 // MODE 1: src has length 2h; X'[y] = X[y] + r (X[y + h] - X[y]) is written to the scratch tables (length h).
@@ -307,6 +291,23 @@ int multi_sumcheck(tpst_ctx* ctx, const uint32_t* const* tabs, size_t B, int n, 
   return TPST_OK;
 }
 
+// the whole polynomials' tables under the context's lock, or an error
+int whole_tables(tpst_ctx* ctx, tpst_poly* const* polys, size_t B, std::vector<const uint32_t*>& tabs) {
+  for (size_t j = 0; j < B; j++) {
+    if (!polys[j]) return fail(ctx, TPST_E_ARG, "null polynomial " + std::to_string(j));
+    if (polys[j]->ctx != ctx) return fail(ctx, TPST_E_ARG, "polynomial of another context");
+    if (polys[j]->n != polys[0]->n) return fail(ctx, TPST_E_ARG, "polynomials differ in num_vars");
+  }
+  std::lock_guard<tpst::CtxMutex> lk(ctx->mu);
+  tabs.resize(B);
+  for (size_t j = 0; j < B; j++) {
+    tabs[j] = polys[j]->q_only ? nullptr : poly_evals(polys[j]);
+    if (!tabs[j]) return fail(ctx, TPST_E_STATE, "operation needs whole polynomials (a column slice or q-only handle)");
+    if ((uintptr_t)tabs[j] & 15) return fail(ctx, TPST_E_ARG, "evaluation table not 16-byte aligned");
+  }
+  return TPST_OK;
+}
+
 }  // namespace tpst
 
 using namespace tpst;
@@ -377,23 +378,6 @@ Fr claim_weights(const uint64_t* gamma, const uint64_t* vals, size_t K, std::vec
     p = mul(p, g);
   }
   return e;
-}
-
-// the whole polynomials' tables under the context's lock, or an error
-int whole_tables(tpst_ctx* ctx, tpst_poly* const* polys, size_t B, std::vector<const uint32_t*>& tabs) {
-  for (size_t j = 0; j < B; j++) {
-    if (!polys[j]) return fail(ctx, TPST_E_ARG, "null polynomial " + std::to_string(j));
-    if (polys[j]->ctx != ctx) return fail(ctx, TPST_E_ARG, "polynomial of another context");
-    if (polys[j]->n != polys[0]->n) return fail(ctx, TPST_E_ARG, "polynomials differ in num_vars");
-  }
-  std::lock_guard<tpst::CtxMutex> lk(ctx->mu);
-  tabs.resize(B);
-  for (size_t j = 0; j < B; j++) {
-    tabs[j] = polys[j]->q_only ? nullptr : poly_evals(polys[j]);
-    if (!tabs[j]) return fail(ctx, TPST_E_STATE, "operation needs whole polynomials (a column slice or q-only handle)");
-    if ((uintptr_t)tabs[j] & 15) return fail(ctx, TPST_E_ARG, "evaluation table not 16-byte aligned");
-  }
-  return TPST_OK;
 }
 
 }  // namespace

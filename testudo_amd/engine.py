@@ -147,7 +147,9 @@ class Context:
               # poly_lincomb.hip: k_fr_lincomb; k_g1_lincomb_rows and the sum of its chains
               "fr_lincomb", "lincomb_rows",
               # poly_multi.hip: round 0, round 1, and the later rounds with the closing bind of the multi-point reduction
-              "multi_round0", "multi_round1", "multi_rounds")
+              "multi_round0", "multi_round1", "multi_rounds",
+              # poly_sumcheck.hip: round 0, round 1, and the later rounds with the closing bind of the product sum-check
+              "sumcheck_round0", "sumcheck_round1", "sumcheck_rounds")
 
     def profile(self, on: bool):
         self.check(self.lib.tpst_profile_enable(self.h, 1 if on else 0), "tpst_profile_enable")

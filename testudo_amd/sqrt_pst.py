@@ -719,6 +719,120 @@ def multi_sumcheck_stages(polys, claims, a, rho):
     return sums, u
 
 
+@dataclass
+class SumcheckOpenProof:
+    """The proof of a product sum-check (include/tpst.h): the round
+    coefficients, the B values at rho and one opening."""
+    rounds: np.ndarray       # (n, D + 1, 4) Fr: the coefficients of every round, constant first
+    u: np.ndarray            # (B, 4) Fr: u_j = f_j(rho)
+    U: np.ndarray            # (12,)
+    pst_proof: np.ndarray    # (m_row, 24)
+    mipp: MippProof
+    rho: np.ndarray = None   # (n, 4): the prover's challenges; not part of the proof, the verifier derives them
+
+
+def _sc_terms(terms, has_tau):
+    """[(coeff, [indices])] -> (the tpst_sc_term array, the round degree D); the library validates the rest"""
+    terms = list(terms)
+    if not terms:
+        raise TpstError("a product sum-check needs at least one term")
+    arr = (_lib.ScTerm * len(terms))()
+    for t, (coeff, idx) in enumerate(terms):
+        idx = [int(j) for j in idx]
+        if len(idx) > 3 or any(j < 0 or j >= 2**32 for j in idx):
+            raise TpstError("a term has at most 3 factors, each a polynomial index")
+        arr[t].deg = len(idx)
+        for k, j in enumerate(idx):
+            arr[t].idx[k] = j
+        for k, limb in enumerate(_u64(coeff, (4,))):
+            arr[t].coeff[k] = int(limb)
+    return arr, max(max(len(idx) for _, idx in terms) + (1 if has_tau else 0), 2)
+
+
+def sumcheck_open(polys, commitments, transcript: PoseidonTranscript, terms, tau=None):
+    """tpst_poly_sumcheck_open: proves e0 = sum_x [eq(tau, x)] sum_t c_t prod_i
+    f_idx_t[i](x) over B committed polynomials of one size with a sum-check and
+    one combined opening.  ``terms``: [(coeff (4,), [indices])], 1..3 indices
+    each; ``tau``: (n, 4) or None; ``commitments``: the (comm_list, T) pairs.
+    Returns (e0 (4,), SumcheckOpenProof, comm_list*, T*, v*); the last three
+    are what ``open_combined`` at the proof's ``rho`` returns."""
+    polys = list(polys)
+    ctx, n, B = polys[0].ctx, polys[0].n, len(polys)
+    arr, D = _sc_terms(terms, tau is not None)
+    tau = None if tau is None else _u64(tau, (n, 4))
+    cl = [_u64(c, (1 << (n // 2), 12)) for c, _ in commitments]
+    tl = [_u64(T, (72,)) for _, T in commitments]
+    hs = (C.c_void_p * B)(*[p.h for p in polys])
+    e0, rounds = np.zeros(4, dtype=np.uint64), np.zeros((n, min(D, 3) + 1, 4), dtype=np.uint64)
+    u, rho = np.zeros((B, 4), dtype=np.uint64), np.zeros((n, 4), dtype=np.uint64)
+    comms = np.zeros((1 << (n // 2), 12), dtype=np.uint64)
+    T, v = np.zeros(72, dtype=np.uint64), np.zeros(4, dtype=np.uint64)
+    pr = _lib.OpenProof()
+    ctx.check(ctx.lib.tpst_poly_sumcheck_open(ctx.h, hs, _ptr_array(cl), _ptr_array(tl), B, C.addressof(arr), len(arr),
+                                              None if tau is None else ptr(tau), C.addressof(transcript.t), ptr(e0),
+                                              ptr(rounds), ptr(u), ptr(rho), ptr(comms), ptr(T), ptr(v), C.byref(pr)),
+              "sumcheck_open")
+    U, pst_proof, mipp = _unpack(pr)
+    return e0, SumcheckOpenProof(rounds, u, U, pst_proof, mipp, rho), comms, T, v
+
+
+def sumcheck_reduce(transcript: PoseidonTranscript, n: int, terms, tau, Ts, e0, rounds, u):
+    """tpst_pst_sumcheck_reduce (host only): the verifier's statement absorb,
+    round checks and final identity on the claimed ``e0``.  Returns rho (n, 4)
+    with ``transcript`` where the combined opening starts, or None (transcript
+    unchanged) when a check fails; misuse raises."""
+    arr, D = _sc_terms(terms, tau is not None)
+    tau = None if tau is None else _u64(tau, (n, 4))
+    tl = [_u64(x, (72,)) for x in Ts]
+    B = len(tl)
+    rho = np.zeros((n, 4), dtype=np.uint64)
+    rc = transcript.lib.tpst_pst_sumcheck_reduce(C.addressof(transcript.t), n, _ptr_array(tl), B, C.addressof(arr),
+                                                 len(arr), None if tau is None else ptr(tau), ptr(_u64(e0, (4,))),
+                                                 ptr(_u64(rounds, (n, min(D, 3) + 1, 4))), ptr(_u64(u, (B, 4))),
+                                                 ptr(rho))
+    if rc == -5:
+        return None
+    if rc:
+        raise TpstError("sumcheck_reduce: rc=%d" % rc)
+    return rho
+
+
+def verify_sumcheck(ctx: Context, transcript: PoseidonTranscript, terms, tau, Ts, e0,
+                    proof: SumcheckOpenProof) -> bool:
+    """tpst_pst_verify_sumcheck: the claim ``e0`` on the terms (and ``tau``)
+    against the B commitments ``Ts`` and one SumcheckOpenProof."""
+    n = len(proof.rounds)
+    arr, D = _sc_terms(terms, tau is not None)
+    tau = None if tau is None else _u64(tau, (n, 4))
+    tl = [_u64(x, (72,)) for x in Ts]
+    B = len(tl)
+    pr = pack_proof(n, proof.U, proof.pst_proof, proof.mipp)
+    rc = ctx.lib.tpst_pst_verify_sumcheck(ctx.h, C.addressof(transcript.t), n, _ptr_array(tl), B, C.addressof(arr),
+                                          len(arr), None if tau is None else ptr(tau), ptr(_u64(e0, (4,))),
+                                          ptr(_u64(proof.rounds, (n, min(D, 3) + 1, 4))), ptr(_u64(proof.u, (B, 4))),
+                                          C.byref(pr))
+    if rc == -5:
+        return False
+    ctx.check(rc, "verify_sumcheck")
+    return True
+
+
+def sumcheck_stages(polys, terms, tau, rho):
+    """tpst_poly_sumcheck_stages (test entry): the device rounds alone on the
+    caller's challenges ``rho`` (n, 4).  Returns (sums (n, D + 1, 4):
+    s_i(0..D), u (B, 4))."""
+    polys = list(polys)
+    ctx, n, B = polys[0].ctx, polys[0].n, len(polys)
+    arr, D = _sc_terms(terms, tau is not None)
+    tau = None if tau is None else _u64(tau, (n, 4))
+    hs = (C.c_void_p * B)(*[p.h for p in polys])
+    sums, u = np.zeros((n, min(D, 3) + 1, 4), dtype=np.uint64), np.zeros((B, 4), dtype=np.uint64)
+    ctx.check(ctx.lib.tpst_poly_sumcheck_stages(ctx.h, hs, B, C.addressof(arr), len(arr),
+                                                None if tau is None else ptr(tau), ptr(_u64(rho, (n, 4))), ptr(sums),
+                                                ptr(u)), "sumcheck_stages")
+    return sums, u
+
+
 def g1_msm_partial_into(ctx: Context, d_bases: int, d_scalars: int, i0: int, i1: int, out) -> None:
     """Points [i0, i1) of a device-resident MSM (Montgomery bases, canonical Fr
     scalars) summed into the int64 tensor ``out`` (24 words, raw XYZZ; a host

@@ -74,6 +74,14 @@ HOT = [
     "k_multi_round<1>",
     "k_multi_round<2>",
     "k_multi_reduce",
+    # the product sum-check's rounds (poly_sumcheck.hip)
+    "k_psc_round<0, 2>",
+    "k_psc_round<1, 2>",
+    "k_psc_round<2, 2>",
+    "k_psc_round<0, 3>",
+    "k_psc_round<1, 3>",
+    "k_psc_round<2, 3>",
+    "k_psc_reduce",
 ]
 
 FIELDS = {
