@@ -604,6 +604,111 @@ int tpst_pst_verify_sumcheck(tpst_ctx* ctx, tpst_transcript* tr, int n, const ui
 int tpst_poly_sumcheck_stages(tpst_ctx* ctx, tpst_poly* const* polys, size_t B, const tpst_sc_term* terms, size_t M,
                               const uint64_t* tau, const uint64_t* rho, uint64_t* sums, uint64_t* u);
 
+/* Lookup argument (LogUp): L witness polynomials a_0..a_{L-1} (1 <= L <= 8)
+ * and one table polynomial t, all whole polynomials of one n in one context,
+ * each committed on its own as (comm_list, T).  The claim: for every l and
+ * every x in {0,1}^n there is a y with a_l(x) = t(y).  The table may hold
+ * repeated values.  A range check is t(y) = y; an opcode or fixed-table lookup
+ * and set membership are the same call.  This protocol is this library's own:
+ * the reference has no counterpart.  It is closed by ONE opening.
+ *
+ * Helper polynomials, built on the device by the prover:
+ *   m(y)   = #{(l, x) : a_l(x) = t(y)}, credited to the FIRST y (lowest index)
+ *            that holds the value and 0 at its repeats: a function of (a, t)
+ *            alone, bit-identical across runs, grids and index capacities;
+ *   h_l(x) = 1 / (beta + a_l(x)),   h_t(y) = m(y) / (beta + t(y)).
+ * The polynomial order used below is a_0..a_{L-1}, t, m, h_0..h_{L-1}, h_t;
+ * B = 2L + 3.
+ *
+ * On the caller's transcript, prover and verifier alike:
+ *  1. tpst_transcript_append_fr of L and n (the Fr of each integer); append_gt
+ *     of T_{a_0}..T_{a_{L-1}}, T_t.
+ *  2. append_gt of T_m; one challenge beta.
+ *  3. append_gt of T_{h_0}..T_{h_{L-1}}, T_{h_t}; n challenges tau_0..tau_{n-1};
+ *     one challenge lambda.
+ *  4. the product sum-check (above), exactly its steps 1-3, on the B
+ *     polynomials with tau (has_tau = 1, D = 3) and the M = 2L + 3 terms
+ *       per l < L: (lambda^l, [h_l, a_l]), (lambda^l beta, [h_l]);
+ *       then (lambda^L, [h_t, t]), (lambda^L beta, [h_t]), (-lambda^L, [m]).
+ *     Its claim is e_0 = sum_{l < L} lambda^l: THE VERIFIER COMPUTES IT, it is
+ *     not taken from the proof.  (Under eq(tau, .) every h_l (beta + a_l) is
+ *     1 and h_t (beta + t) - m is 0.)  It ends in rho and u_j = f_j(rho).
+ *  5. s_l = h_l(1/2, .., 1/2) and s_t = h_t(1/2, .., 1/2), 1/2 = (r + 1) / 2;
+ *     the check is sum_l s_l = s_t.  For a multilinear h,
+ *     sum_x h(x) = 2^n h(1/2, .., 1/2): this is the LogUp identity
+ *     sum_l sum_x 1 / (beta + a_l(x)) = sum_y m(y) / (beta + t(y)) without a
+ *     second sum-check.
+ *  6. the multi-point opening (above), exactly its steps 1-4, on all B
+ *     polynomials with the K = 3L + 4 claims f_j(rho) = u_j for j = 0..B-1,
+ *     then h_l(1/2, .., 1/2) = s_l for l < L, then h_t(1/2, .., 1/2) = s_t.
+ *     It ends in one combined opening at its own point rho'.
+ * The proof: T_m and T_{h_0}..T_{h_t} (T_helpers, (L + 2) x 72); the n x 4
+ * round coefficients (sc_rounds) and the 2L + 3 values u; the L + 1 values s
+ * (s_0..s_{L-1}, s_t); the multi-point reduction's n x 3 coefficients
+ * (mp_rounds) and its 2L + 3 final values (mp_u); one tpst_open_proof.  comms
+ * and Ts are the L + 1 commitments of a_0..a_{L-1}, t in that order.  NOT PART
+ * OF THIS INTERFACE: the proof's wire format, a sharded (multi-rank) form,
+ * tables of another n than the witnesses, vector (multi-column) lookups, and
+ * merging with a caller's own sum-check.
+ *
+ * SOUNDNESS: (L + 1) 2^n / r for the identity in beta (it needs L 2^n < r,
+ * which always holds), (n + L) / r for tau and lambda, plus the bounds of the
+ * product sum-check and of the multi-point opening.  IT HOLDS ONLY BECAUSE
+ * beta IS DRAWN AFTER T_m IS ABSORBED, tau AND lambda ARE DRAWN AFTER EVERY T_h
+ * IS ABSORBED, AND WHATEVER FIXED T_a AND T_t IS ON THE TRANSCRIPT BEFORE THE
+ * CALL: a caller that replays these steps itself must keep that order.  With a
+ * beta the prover knows before it commits to m, a false m can be made to
+ * satisfy the identity.
+ *
+ * tpst_poly_lookup_open: the prover.  Builds m (an index of the table, one
+ *   probe per witness entry), commits it, draws beta, builds every h (a
+ *   batched inversion) and commits it, draws tau and lambda, runs the product
+ *   sum-check's rounds on the device and tpst_poly_open_multi on the claims of
+ *   step 6; writes every proof part, rho' (rho, n Fr) and what the combined
+ *   opening writes (comm_list*, T*, v*, the proof).  The handles' tables are
+ *   read, never written; the helper handles are freed before return.  tr ends
+ *   as tpst_poly_open_multi leaves it and is unchanged on any error.
+ *   THE PROVER DOES CHECK MEMBERSHIP (m does not exist otherwise): a witness
+ *   entry that is not in the table is TPST_E_ARG, and tpst_last_error names the
+ *   least (l, x).  beta + value = 0 (probability <= (L + 1) 2^n / r) is
+ *   TPST_E_ARG too.  TPST_E_ARG also: a null argument, L out of range,
+ *   polynomials of different n or of another context, n + 3 > 32 or
+ *   L 2^n >= 2^32 (the counts are u32), a T with a coefficient >= p.
+ *   TPST_E_STATE: a handle that is not a whole polynomial, no SRS loaded.
+ * tpst_pst_lookup_reduce: HOST ONLY, no context: the verifier's steps 1-5 and
+ *   the multi-point reduction (steps 1-3 of step 6), composed from
+ *   tpst_pst_sumcheck_reduce and tpst_pst_multi_reduce.  On TPST_OK rho' is
+ *   written and tr stands where the combined opening's challenge
+ *   (tpst_pst_combine_challenge on rho', all B T and mp_u) starts.
+ *   TPST_E_VERIFY: any failed check, any scalar >= r, any T with a coefficient
+ *   >= p.  TPST_E_ARG: misuse (null argument, bad n, n + 3 > 32, L out of
+ *   range).  tr is unchanged on any failure.
+ * tpst_pst_verify_lookup: tpst_pst_lookup_reduce, tpst_pst_combine_challenge,
+ *   tpst_pst_verify_combined.  TPST_OK or TPST_E_VERIFY; TPST_E_ARG also for
+ *   sizes that do not match n; TPST_E_STATE: no SRS loaded.  tr is changed only
+ *   on TPST_OK.
+ * tpst_poly_lookup_stages: test entry.  The device stages alone on the
+ *   caller's beta (no SRS needed): m (2^n Fr), h = h_0..h_{L-1}, h_t
+ *   ((L + 1) x 2^n Fr) and s = s_0..s_{L-1}, s_t (L + 1 Fr), all canonical.
+ *   Errors as tpst_poly_lookup_open; beta >= r is TPST_E_ARG.
+ * Test hooks (environment): TPST_LOOKUP_GRID=g caps the workgroups of the
+ * lookup kernels; TPST_LOOKUP_SLOTS_LOG2=k sets the index capacity to 2^k
+ * slots (default n + 1, twice the table; k = n is load factor 1; k < n or
+ * k > 31 is TPST_E_ARG).  No output depends on either. */
+int tpst_poly_lookup_open(tpst_ctx* ctx, tpst_poly* const* wits, size_t L, tpst_poly* table,
+                          const uint64_t* const* comms, const uint64_t* const* Ts, tpst_transcript* tr,
+                          uint64_t* T_helpers, uint64_t* sc_rounds, uint64_t* u, uint64_t* s, uint64_t* mp_rounds,
+                          uint64_t* mp_u, uint64_t* rho, uint64_t* comms_out, uint64_t* T_out, uint64_t* v_out,
+                          tpst_open_proof* proof);
+int tpst_pst_lookup_reduce(tpst_transcript* tr, int n, size_t L, const uint64_t* const* Ts, const uint64_t* T_helpers,
+                           const uint64_t* sc_rounds, const uint64_t* u, const uint64_t* s, const uint64_t* mp_rounds,
+                           const uint64_t* mp_u, uint64_t* rho);
+int tpst_pst_verify_lookup(tpst_ctx* ctx, tpst_transcript* tr, int n, size_t L, const uint64_t* const* Ts,
+                           const uint64_t* T_helpers, const uint64_t* sc_rounds, const uint64_t* u, const uint64_t* s,
+                           const uint64_t* mp_rounds, const uint64_t* mp_u, const tpst_open_proof* proof);
+int tpst_poly_lookup_stages(tpst_ctx* ctx, tpst_poly* const* wits, size_t L, tpst_poly* table, const uint64_t* beta,
+                            uint64_t* m, uint64_t* h, uint64_t* s);
+
 /* ---- MultilinearPC single calls (ark-poly-commit fork) --
  * Against the loaded SRS; a polynomial of nv <= ck.nv variables uses level
  * ck.nv - nv.  evals: 2^nv canonical Fr (to_evaluations order); point: nv Fr,

@@ -115,6 +115,13 @@ PROTOTYPES = [
     ("tpst_pst_verify_sumcheck", C.c_int, [_vp, _vp, C.c_int, C.POINTER(_u64p), _sz, _vp, _sz, _u64p, _u64p, _u64p,
                                            _u64p, _vp]),
     ("tpst_poly_sumcheck_stages", C.c_int, [_vp, C.POINTER(_vp), _sz, _vp, _sz, _u64p, _u64p, _u64p, _u64p]),
+    ("tpst_poly_lookup_open", C.c_int, [_vp, C.POINTER(_vp), _sz, _vp, C.POINTER(_u64p), C.POINTER(_u64p), _vp, _u64p,
+                                        _u64p, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p, _vp]),
+    ("tpst_pst_lookup_reduce", C.c_int, [_vp, C.c_int, _sz, C.POINTER(_u64p), _u64p, _u64p, _u64p, _u64p, _u64p, _u64p,
+                                         _u64p]),
+    ("tpst_pst_verify_lookup", C.c_int, [_vp, _vp, C.c_int, _sz, C.POINTER(_u64p), _u64p, _u64p, _u64p, _u64p, _u64p,
+                                         _u64p, _vp]),
+    ("tpst_poly_lookup_stages", C.c_int, [_vp, C.POINTER(_vp), _sz, _vp, _u64p, _u64p, _u64p, _u64p]),
     ("tpst_mlpc_commit", C.c_int, [_vp, _u64p, C.c_int, _u64p]),
     ("tpst_mlpc_commit_g2", C.c_int, [_vp, _u64p, C.c_int, _u64p]),
     ("tpst_mlpc_open", C.c_int, [_vp, _u64p, C.c_int, _u64p, _u64p]),

@@ -65,6 +65,9 @@ enum MsmStage {
   // poly_sumcheck.hip, the product sum-check (round kernel + reduce launch): round 0 (reads the handles); round 1
   // (binds from the handles, writes the scratch tables); every later round and the closing bind
   ST_SC_ROUND0, ST_SC_ROUND1, ST_SC_ROUNDS,
+  // lookup.hip, the lookup argument's helper tables: the index of the table; the probes and counts (m included);
+  // the batched inversions (every h); the sums of the h tables (their values at the 1/2 point)
+  ST_LK_INDEX, ST_LK_COUNT, ST_LK_INVERSE, ST_LK_SUMS,
   N_STAGES
 };
 

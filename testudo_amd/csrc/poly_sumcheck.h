@@ -6,6 +6,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <functional>
+#include <vector>
+#include "../../include/tpst.h"
 #include "msm.h"
 
 struct tpst_ctx;
@@ -61,5 +63,11 @@ hipError_t psc_finals(hipStream_t s, const uint32_t* d_scr, size_t scr_stride, i
 using PscChallenge = std::function<int(int round, const uint64_t* evals, const uint64_t* coeffs, uint64_t* rho)>;
 int psc_sumcheck(tpst_ctx* ctx, const uint32_t* const* tabs, size_t B, int n, const PscTerm* terms, size_t M,
                 const uint64_t* tau, int deg, const PscChallenge& challenge, uint64_t* u);
+
+// For a prover that runs psc_sumcheck inside a protocol of its own (lookup.hip): step 1 of the product sum-check on
+// t (non-zero: a T_j with a coefficient >= p), and the kernels' terms c_t R^deg_t of validated public terms.
+int psc_absorb_statement(tpst_transcript* t, int n, size_t B, const uint64_t* const* Ts, const tpst_sc_term* terms,
+                         size_t M, const uint64_t* tau, const uint64_t* e0);
+std::vector<PscTerm> psc_device_terms(const tpst_sc_term* terms, size_t M);
 
 }  // namespace tpst

@@ -358,9 +358,11 @@ bool statement_canonical(int n, const tpst_sc_term* terms, size_t M, const uint6
   return true;
 }
 
+}  // namespace
+
 // step 1: the statement
-int absorb_statement(tpst_transcript* t, int n, size_t B, const uint64_t* const* Ts, const tpst_sc_term* terms, size_t M,
-                     const uint64_t* tau, const uint64_t* e0) {
+int tpst::psc_absorb_statement(tpst_transcript* t, int n, size_t B, const uint64_t* const* Ts, const tpst_sc_term* terms,
+                               size_t M, const uint64_t* tau, const uint64_t* e0) {
   int rc = append_int(t, B) | append_int(t, M) | append_int(t, (uint64_t)n) | append_int(t, tau ? 1 : 0);
   for (size_t j = 0; j < B; j++) rc |= tpst_transcript_append_gt(t, Ts[j]);
   for (size_t k = 0; k < M; k++) {
@@ -374,7 +376,7 @@ int absorb_statement(tpst_transcript* t, int n, size_t B, const uint64_t* const*
 }
 
 // the kernels' terms: c_t R^deg_t (poly_sumcheck.h)
-std::vector<PscTerm> device_terms(const tpst_sc_term* terms, size_t M) {
+std::vector<PscTerm> tpst::psc_device_terms(const tpst_sc_term* terms, size_t M) {
   std::vector<PscTerm> out(M);
   for (size_t t = 0; t < M; t++) {
     out[t].deg = terms[t].deg;
@@ -386,6 +388,8 @@ std::vector<PscTerm> device_terms(const tpst_sc_term* terms, size_t M) {
   }
   return out;
 }
+
+namespace {
 
 // what prover and stages entry check alike; n and D out
 int prover_args(tpst_ctx* ctx, tpst_poly* const* polys, size_t B, const tpst_sc_term* terms, size_t M,
@@ -410,7 +414,7 @@ extern "C" int tpst_poly_sumcheck_stages(tpst_ctx* ctx, tpst_poly* const* polys,
   if (int rc = prover_args(ctx, polys, B, terms, M, tau, tabs, n, D)) return rc;
   for (int i = 0; i < n; i++)
     if (!fr_ok(rho + 4 * i)) return fail(ctx, TPST_E_ARG, "challenge >= r");
-  const std::vector<PscTerm> dt = device_terms(terms, M);
+  const std::vector<PscTerm> dt = psc_device_terms(terms, M);
   return psc_sumcheck(ctx, tabs.data(), B, n, dt.data(), M, tau, D,
                      [&](int i, const uint64_t* evals, const uint64_t*, uint64_t* r) {
                        memcpy(sums + 4 * (size_t)(D + 1) * i, evals, 32 * (size_t)(D + 1));
@@ -439,13 +443,13 @@ extern "C" int tpst_poly_sumcheck_open(tpst_ctx* ctx, tpst_poly* const* polys, c
     std::lock_guard<tpst::CtxMutex> lk(ctx->mu);
     if (!srs_of(ctx)) return fail(ctx, TPST_E_STATE, "no SRS loaded");
   }
-  const std::vector<PscTerm> dt = device_terms(terms, M);
+  const std::vector<PscTerm> dt = psc_device_terms(terms, M);
   tpst_transcript t = *tr;  // tr changes only on success
   const int rc = psc_sumcheck(ctx, tabs.data(), B, n, dt.data(), M, tau, D,
                              [&](int i, const uint64_t* evals, const uint64_t* coeffs, uint64_t* r) {
                                if (i == 0) {  // the claim is known now: e_0 = s_0(0) + s_0(1); then step 1
                                  fr_out(add(fr_canon(evals), fr_canon(evals + 4)), e0);
-                                 if (absorb_statement(&t, n, B, Ts, terms, M, tau, e0) != TPST_OK)
+                                 if (psc_absorb_statement(&t, n, B, Ts, terms, M, tau, e0) != TPST_OK)
                                    return fail(ctx, TPST_E_ARG, "a T_j with a coefficient >= p");
                                }
                                uint64_t* out = rounds + 4 * (size_t)(D + 1) * i;
@@ -483,7 +487,7 @@ extern "C" int tpst_pst_sumcheck_reduce(tpst_transcript* tr, int n, const uint64
   for (int i = 0; i < (D + 1) * n; i++)
     if (!fr_ok(rounds + 4 * (size_t)i)) return TPST_E_VERIFY;
   tpst_transcript t = *tr;  // tr changes only on success
-  if (absorb_statement(&t, n, B, Ts, terms, M, tau, e0) != TPST_OK) return TPST_E_VERIFY;
+  if (psc_absorb_statement(&t, n, B, Ts, terms, M, tau, e0) != TPST_OK) return TPST_E_VERIFY;
   Fr e = fr_canon(e0);
   std::vector<Fr> rs(n);
   std::vector<uint64_t> rc(4 * (size_t)n);

@@ -149,7 +149,9 @@ class Context:
               # poly_multi.hip: round 0, round 1, and the later rounds with the closing bind of the multi-point reduction
               "multi_round0", "multi_round1", "multi_rounds",
               # poly_sumcheck.hip: round 0, round 1, and the later rounds with the closing bind of the product sum-check
-              "sumcheck_round0", "sumcheck_round1", "sumcheck_rounds")
+              "sumcheck_round0", "sumcheck_round1", "sumcheck_rounds",
+              # lookup.hip: the table's index; probes and counts; the batched inversions; the sums of the h tables
+              "lookup_index", "lookup_count", "lookup_inverse", "lookup_sums")
 
     def profile(self, on: bool):
         self.check(self.lib.tpst_profile_enable(self.h, 1 if on else 0), "tpst_profile_enable")

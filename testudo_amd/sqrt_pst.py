@@ -833,6 +833,119 @@ def sumcheck_stages(polys, terms, tau, rho):
     return sums, u
 
 
+@dataclass
+class LookupProof:
+    """The proof of a lookup argument (include/tpst.h): the helper
+    commitments, the product sum-check, the values at the 1/2 point, the
+    multi-point reduction and one opening."""
+    T_m: np.ndarray          # (72,) GT
+    T_h: np.ndarray          # (L + 1, 72) GT: T_{h_0}..T_{h_{L-1}}, T_{h_t}
+    rounds: np.ndarray       # (n, 4, 4) Fr: the sum-check's coefficients, constant first
+    u: np.ndarray            # (2L + 3, 4) Fr: u_j = f_j(rho)
+    s: np.ndarray            # (L + 1, 4) Fr: s_0..s_{L-1}, s_t
+    mp_rounds: np.ndarray    # (n, 3, 4) Fr: the multi-point reduction's coefficients
+    mp_u: np.ndarray         # (2L + 3, 4) Fr: its final values f_j(rho')
+    U: np.ndarray            # (12,)
+    pst_proof: np.ndarray    # (m_row, 24)
+    mipp: MippProof
+    rho: np.ndarray = None   # (n, 4): rho', the combined opening's point; not part of the proof
+
+    def T_helpers(self) -> np.ndarray:
+        """T_m, then every T_h: (L + 2, 72), the C-ABI's layout"""
+        return np.ascontiguousarray(np.concatenate([_u64(self.T_m, (1, 72)), _u64(self.T_h).reshape(-1, 72)]))
+
+
+def range_table(ctx: Context, n: int) -> Polynomial:
+    """The table of a range check: t(y) = y for y < 2^n."""
+    Z = np.zeros((1 << n, 4), dtype=np.uint64)
+    Z[:, 0] = np.arange(1 << n, dtype=np.uint64)
+    return Polynomial.from_evaluations(ctx, Z)
+
+
+def lookup_open(witnesses, table: Polynomial, commitments, transcript: PoseidonTranscript):
+    """tpst_poly_lookup_open: proves that every entry of every witness
+    polynomial occurs in ``table``, with one opening.  ``commitments``: the
+    (comm_list, T) pairs of the witnesses, then of the table.  A witness entry
+    that is not in the table raises.  Returns (LookupProof, comm_list*, T*,
+    v*); the last three are what the combined opening at the proof's ``rho``
+    returns."""
+    wits = list(witnesses)
+    ctx, n, L = table.ctx, table.n, len(wits)
+    B = 2 * L + 3
+    cl = [_u64(c, (1 << (n // 2), 12)) for c, _ in commitments]
+    tl = [_u64(T, (72,)) for _, T in commitments]
+    if len(cl) != L + 1:
+        raise TpstError("lookup_open: one commitment per witness, then the table's")
+    hs = (C.c_void_p * max(L, 1))(*[p.h for p in wits])
+    Th = np.zeros((L + 2, 72), dtype=np.uint64)
+    rounds, mp_rounds = np.zeros((n, 4, 4), dtype=np.uint64), np.zeros((n, 3, 4), dtype=np.uint64)
+    u, mp_u = np.zeros((B, 4), dtype=np.uint64), np.zeros((B, 4), dtype=np.uint64)
+    s, rho = np.zeros((L + 1, 4), dtype=np.uint64), np.zeros((n, 4), dtype=np.uint64)
+    comms = np.zeros((1 << (n // 2), 12), dtype=np.uint64)
+    T, v = np.zeros(72, dtype=np.uint64), np.zeros(4, dtype=np.uint64)
+    pr = _lib.OpenProof()
+    ctx.check(ctx.lib.tpst_poly_lookup_open(ctx.h, hs, L, table.h, _ptr_array(cl), _ptr_array(tl),
+                                            C.addressof(transcript.t), ptr(Th), ptr(rounds), ptr(u), ptr(s),
+                                            ptr(mp_rounds), ptr(mp_u), ptr(rho), ptr(comms), ptr(T), ptr(v),
+                                            C.byref(pr)), "lookup_open")
+    U, pst_proof, mipp = _unpack(pr)
+    return LookupProof(Th[0].copy(), Th[1:].copy(), rounds, u, s, mp_rounds, mp_u, U, pst_proof, mipp, rho), comms, T, v
+
+
+def _lookup_args(n, Ts, proof: LookupProof):
+    tl = [_u64(x, (72,)) for x in Ts]
+    L = len(tl) - 1
+    B = 2 * L + 3
+    return tl, L, (proof.T_helpers().reshape(L + 2, 72), _u64(proof.rounds, (n, 4, 4)), _u64(proof.u, (B, 4)),
+                   _u64(proof.s, (L + 1, 4)), _u64(proof.mp_rounds, (n, 3, 4)), _u64(proof.mp_u, (B, 4)))
+
+
+def lookup_reduce(transcript: PoseidonTranscript, n: int, Ts, proof: LookupProof):
+    """tpst_pst_lookup_reduce (host only): the verifier's transcript steps,
+    the product sum-check, sum_l s_l = s_t and the multi-point reduction.
+    ``Ts``: the T of every witness, then the table's.  Returns rho' (n, 4) with
+    ``transcript`` where the combined opening's challenge starts, or None
+    (transcript unchanged) when a check fails; misuse raises."""
+    tl, L, arrs = _lookup_args(n, Ts, proof)
+    rho = np.zeros((n, 4), dtype=np.uint64)
+    rc = transcript.lib.tpst_pst_lookup_reduce(C.addressof(transcript.t), n, L, _ptr_array(tl),
+                                               *[ptr(a) for a in arrs], ptr(rho))
+    if rc == -5:
+        return None
+    if rc:
+        raise TpstError("lookup_reduce: rc=%d" % rc)
+    return rho
+
+
+def verify_lookup(ctx: Context, transcript: PoseidonTranscript, Ts, proof: LookupProof) -> bool:
+    """tpst_pst_verify_lookup: every entry of the polynomials behind
+    ``Ts[:-1]`` occurs in the table behind ``Ts[-1]``."""
+    n = len(proof.rounds)
+    tl, L, arrs = _lookup_args(n, Ts, proof)
+    pr = pack_proof(n, proof.U, proof.pst_proof, proof.mipp)
+    rc = ctx.lib.tpst_pst_verify_lookup(ctx.h, C.addressof(transcript.t), n, L, _ptr_array(tl),
+                                        *[ptr(a) for a in arrs], C.byref(pr))
+    if rc == -5:
+        return False
+    ctx.check(rc, "verify_lookup")
+    return True
+
+
+def lookup_stages(witnesses, table: Polynomial, beta):
+    """tpst_poly_lookup_stages (test entry): the device stages alone on the
+    caller's ``beta`` (4,).  Returns (m (2^n, 4), h (L + 1, 2^n, 4): h_0..
+    h_{L-1}, h_t, s (L + 1, 4))."""
+    wits = list(witnesses)
+    ctx, n, L = table.ctx, table.n, len(wits)
+    hs = (C.c_void_p * max(L, 1))(*[p.h for p in wits])
+    m = np.zeros((1 << n, 4), dtype=np.uint64)
+    h = np.zeros((L + 1, 1 << n, 4), dtype=np.uint64)
+    s = np.zeros((L + 1, 4), dtype=np.uint64)
+    ctx.check(ctx.lib.tpst_poly_lookup_stages(ctx.h, hs, L, table.h, ptr(_u64(beta, (4,))), ptr(m), ptr(h), ptr(s)),
+              "lookup_stages")
+    return m, h, s
+
+
 def g1_msm_partial_into(ctx: Context, d_bases: int, d_scalars: int, i0: int, i1: int, out) -> None:
     """Points [i0, i1) of a device-resident MSM (Montgomery bases, canonical Fr
     scalars) summed into the int64 tensor ``out`` (24 words, raw XYZZ; a host

@@ -82,6 +82,13 @@ HOT = [
     "k_psc_round<1, 3>",
     "k_psc_round<2, 3>",
     "k_psc_reduce",
+    # the lookup argument's helper tables (lookup.hip)
+    "k_lk_index",
+    "k_lk_count",
+    "k_lk_counts_fr",
+    "k_lk_inverse<true>",
+    "k_lk_inverse<false>",
+    "k_lk_sum",
 ]
 
 FIELDS = {
